@@ -24,6 +24,13 @@ into equal-atom shards (SURVEY 8e), one per rank, no data-path collective;
 RCCL carries only the barrier and the final MAX(time) / SUM(units).  The weak
 scaling rate (every rank its own proteome) is printed as a secondary field.
 
+A plain run (`--gpus 1 --steps N --warmup W`) does only what `value` needs: it sets up, pre-warms, warms up, times
+the N steps and prints the line (with the per-kernel times of those steps).  `--full` adds everything else the
+benchmark measures and checks: the CPU baseline and the parity diff against it, the candidate counts behind `roofline`,
+the host-to-host, one-at-a-time, hashed-ids, weak-scaling, config-5, real-coordinates, files-mode and per-call legs.
+A secondary leg's option given explicitly runs it with or without `--full`.  `--dump-outputs DIR` writes what the
+timed path computed in its last step (per-atom and per-residue SASA, float32) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0 (field notes: DESIGN.md "Measurement").
 """
 import argparse
@@ -42,6 +49,10 @@ VALU_PEAK_TFLOPS = 157.3        # f32 vector peak (MI355X_MICROARCH.md)
 PROBE = 1.4
 N_POINTS = 100
 PMC_FILE = os.path.join("profiles", "pmc_occlusion.json")
+# the secondary legs' options: their value under --full when not given (a plain run: 0, the leg does not run)
+FULL_DEFAULTS = {"cpu_seconds": 15.0, "h2h_steps": 10, "hashed_ids_steps": 20, "two_steps": 40, "weak_steps": 5,
+                 "config5_steps": 30, "real_steps": 10, "files": 1000, "per_call_seconds": 1.0}
+DUMP_BYTES = 60_000_000   # --dump-outputs: all arrays together, under 64 MB with their .npy headers
 
 
 def parse_args(argv=None):
@@ -57,27 +68,27 @@ def parse_args(argv=None):
     p.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                    help="strong: one proteome sharded over the ranks (default); weak: one proteome per rank")
     p.add_argument("--n-points", type=int, default=None)
-    p.add_argument("--cpu-seconds", type=float, default=15.0,
+    p.add_argument("--cpu-seconds", type=float, default=None,
                    help="target wall time of the CPU baseline sample (0 disables it and the parity diff)")
-    p.add_argument("--h2h-steps", type=int, default=10,
+    p.add_argument("--h2h-steps", type=int, default=None,
                    help="timed steps of the host-to-host leg (0 disables it)")
-    p.add_argument("--hashed-ids-steps", type=int, default=20,
+    p.add_argument("--hashed-ids-steps", type=int, default=None,
                    help="steps of the secondary measurement with unordered ids (0 = skip)")
-    p.add_argument("--two-steps", type=int, default=40,
+    p.add_argument("--two-steps", type=int, default=None,
                    help="steps of the secondary one-batch-at-a-time measurement (0 = skip)")
     p.add_argument("--shard-of", type=int, default=0,
                    help="one GPU only: run rank 0's shard of an M-way strong-scaling split (what each of M GPUs would get)")
-    p.add_argument("--weak-steps", type=int, default=5,
+    p.add_argument("--weak-steps", type=int, default=None,
                    help="timed steps of the secondary weak-scaling measurement at N > 1 (0 disables it)")
-    p.add_argument("--config5-steps", type=int, default=30,
+    p.add_argument("--config5-steps", type=int, default=None,
                    help="timed steps of the secondary 1M-atom / 960-point measurement (BASELINE.json configs[4]; 0 = skip)")
-    p.add_argument("--real-steps", type=int, default=10,
+    p.add_argument("--real-steps", type=int, default=None,
                    help="steps of the real_coords leg (the reference's 88-file quality set, tiled to the proteome's size; 0: skip)")
-    p.add_argument("--files", type=int, default=1000,
+    p.add_argument("--files", type=int, default=None,
                    help="files of the secondary directory-mode measurement (files on /dev/shm -> residue values; 0 = skip)")
     p.add_argument("--e2e-files", type=int, default=4363,
                    help="files of the files_mode.end_to_end leg (files in -> one JSON file per input out, one call; 0: skip)")
-    p.add_argument("--per-call-seconds", type=float, default=1.0,
+    p.add_argument("--per-call-seconds", type=float, default=None,
                    help="seconds per leg of the secondary drop-in measurement: rsasa_calculate_sasa_internal once per "
                         "structure from 1 and from 16 host threads (0 = skip)")
     p.add_argument("--no-ids", action="store_true", help="pass id = NULL (all atoms distinct)")
@@ -91,7 +102,21 @@ def parse_args(argv=None):
                         "per-rank verdicts (small --structures counts: the oracle runs on the rank's whole shard)")
     p.add_argument("--dry-run", action="store_true",
                    help="CPU only (gloo): launcher, sharding and aggregation without any GPU work")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="also run every secondary leg and check (the options above that are not given take their "
+                        "defaults: " + ", ".join(f"--{k.replace('_', '-')} {v:g}" for k, v in FULL_DEFAULTS.items())
+                        + ") and the candidate counts behind `roofline`; without it they are 0 and the line carries "
+                          "the timed steps only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the timed path's outputs of its last step as DIR/<name>.npy (float32; a fixed sample "
+                        "when they exceed 60 MB)")
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    for k, v in FULL_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v if args.full else 0)
+    return args
 
 
 def self_launch(args):
@@ -265,6 +290,18 @@ def parity(batch, idx, want_atoms, got_atoms, got_res):
     return {"max_abs": max_abs, "n_mismatch": n_bad, "atoms_compared": n_cmp, "residue_max_abs": r_max,
             "residue_n_mismatch": r_bad, "residues_compared": r_cmp, "tolerance": 1e-4,
             "against": "oracle/sasa_oracle.c on the cpu_baseline sample"}
+
+
+def dump_outputs(directory, arrays, budget):
+    """Every array as DIR/<name>.npy in float32.  Over `budget` bytes in all, each is cut to the same share of its
+    elements: a sample drawn with a fixed seed, kept in index order (the same elements in every run of a workload)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, a.size * budget // total, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def kernel_source_hash():
@@ -693,12 +730,14 @@ def main():
     stream = None  # the context's own launch streams (one per batch in flight); its HIP events time the kernels on them
     run = DeviceRun(ctx, batch, n_points, dev, not args.no_ids, stream)
 
-    # candidate counts K_i (deterministic for a given input) for the algorithmic byte count
-    kcount = torch.zeros(batch.n_atoms, dtype=torch.int32, device=dev)
+    # One untimed step in every run, whatever --warmup says (it loads the kernels and allocates the first workspace);
+    # under --full it also returns the candidate counts K_i (deterministic for a given input) for the algorithmic bytes.
+    kcount = torch.zeros(batch.n_atoms, dtype=torch.int32, device=dev) if args.full else None
     run.step(kcount)
-    k_sum = int(kcount.to(torch.int64).sum().item())
-    del kcount
-    algorithmic_bytes = 20 * batch.n_atoms + 16 * k_sum  # 16 + 16*K + 4 per atom
+    if args.full:
+        k_sum = int(kcount.to(torch.int64).sum().item())
+        del kcount
+        algorithmic_bytes = 20 * batch.n_atoms + 16 * k_sum  # 16 + 16*K + 4 per atom
 
     # The device's clocks first.  After an idle stretch - and the second workspace's allocation inside the first overlapped
     # enqueue below is one of tens of milliseconds - an occlusion launch takes up to a quarter longer and about ten launches
@@ -755,8 +794,13 @@ def main():
                                                        batch.n_atoms)
     got_atoms = run.outs[(args.steps - 1) % 2][0].cpu().numpy()
     got_res = run.outs[(args.steps - 1) % 2][1].cpu().numpy()
-    outputs_equal = args.steps < 2 or bool(torch.equal(run.outs[0][1], run.outs[1][1]) and
-                                             torch.equal(run.outs[0][0], run.outs[1][0]))
+    if args.full:
+        outputs_equal = args.steps < 2 or bool(torch.equal(run.outs[0][1], run.outs[1][1]) and
+                                                 torch.equal(run.outs[0][0], run.outs[1][0]))
+    if args.dump_outputs:
+        suffix = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {"atom_sasa" + suffix: got_atoms, "residue_sasa" + suffix: got_res},
+                     DUMP_BYTES // world)
 
     # ---- every rank's shard against the oracle (tests: the N > 1 path with the real engine on every rank) ----
     shard_parity = None
@@ -941,7 +985,8 @@ def main():
         occl = float(np.mean(occl_ms))
         pmc, pmc_state = load_pmc("pmc_occlusion.json")
         full_batch = world == 1 and batch.n_structures == 4363
-        if args.workload == "proteome":
+        roofline = None
+        if args.full and args.workload == "proteome":
             achieved = algorithmic_bytes / (occl * 1e-3) / 1e9
             roofline = {"bound": "valu", "kernel": "k_occlusion", "achieved": round(achieved, 2),
                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBPS, 4),
@@ -959,7 +1004,7 @@ def main():
                 # that launch's own cycle count: a modelled occupancy, both variants printed (profiles/README.md)
                 roofline["alu_busy"] = pmc["alu_busy"]
                 roofline["insts_per_launch"] = {"vector": pmc.get("valu_insts_per_launch"), "scalar": pmc.get("salu_insts_per_launch")}
-        else:
+        elif args.full:
             # config 5 is bound by the vector ALUs: no HBM fraction is claimed.  Utilisation =
             # vector instructions the occlusion launch executed (rocprofv3 SQ_INSTS_VALU, profiles/) x 64
             # lanes x 2 flop, as if every one were a full-wave FMA, against the f32 vector peak.
@@ -992,11 +1037,9 @@ def main():
             "data": "synthetic",
             "config": {"workload": name, "inputs": "resident in HBM (SoA + offsets), outputs left in HBM",
                        "stepping": "two batches in flight (step k + 1 enqueued before step k is waited for)",
-                       "outputs_of_both_workspaces_equal": outputs_equal,
                        "structures_total": int(total_structures), "atoms_total": int(total_atoms),
                        "structures_rank0": batch.n_structures, "atoms_rank0": batch.n_atoms,
                        "residues_rank0": batch.n_residues,
-                       "candidates_per_atom": round(k_sum / max(batch.n_atoms, 1), 2),
                        "grid_cells_rank0": cells[0],
                        "atoms_per_s": round(total_atoms * args.steps / elapsed, 1),
                        "ids": not args.no_ids,
@@ -1011,7 +1054,6 @@ def main():
                        "gpu_pci": numa["gpu_pci"],
                        "parallelism": f"{world} rank(s), one per GPU, independent shards, no data-path "
                                       f"collective"},
-            "roofline": roofline,
             "kernel_ms": {"grid_build": round(float(np.mean(grid_ms)), 4),
                           "occlusion": round(occl, 4),
                           "residue_sums": round(float(np.mean(agg_ms)), 4),
@@ -1020,6 +1062,10 @@ def main():
                                   "wall time here includes that wait: alone it takes one_at_a_time.grid_build_kernel_ms), "
                                   "occlusion kernels run one after the other"},
         }
+        if args.full:
+            line["config"]["outputs_of_both_workspaces_equal"] = outputs_equal
+            line["config"]["candidates_per_atom"] = round(k_sum / max(batch.n_atoms, 1), 2)
+            line["roofline"] = roofline
         if len(step_done) > 2:
             d = np.diff(np.array(step_done)) * 1e3  # (the first step also carries the second one's enqueue: left out)
             line["ms_per_step_min"] = round(float(d.min()), 4)

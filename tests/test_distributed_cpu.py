@@ -89,3 +89,24 @@ def test_numa_bind_leaves_single_node_machines_alone(tmp_path):
     assert bench.numa_bind(None)["numa_node"] is None
     assert bench.numa_bind("0000:ff:00.0", str(tmp_path))["numa_node"] is None  # no such device
     assert bench.parse_cpulist("0-3,8,10-11") == {0, 1, 2, 3, 8, 10, 11}
+
+
+def test_plain_run_options_and_output_dump(tmp_path):
+    """A plain run leaves every secondary leg off; --full gives them their defaults; a value given explicitly holds either
+    way.  --dump-outputs writes float32 .npy files; over its budget, the same seeded sample in index order every time."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    plain, full = bench.parse_args(["--steps", "3"]), bench.parse_args(["--full", "--two-steps", "2"])
+    assert not plain.full and all(getattr(plain, k) == 0 for k in bench.FULL_DEFAULTS)
+    assert full.two_steps == 2 and all(getattr(full, k) == v for k, v in bench.FULL_DEFAULTS.items() if k != "two_steps")
+    assert bench.parse_args(["--real-steps", "4"]).real_steps == 4
+    a, r = np.arange(1000, dtype=np.float32), np.arange(100, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "all"), {"atom_sasa": a, "residue_sasa": r}, 10**6)
+    assert np.array_equal(np.load(tmp_path / "all" / "atom_sasa.npy"), a)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"atom_sasa": a, "residue_sasa": r}, 2200)  # half of the 4400 bytes
+    s = np.load(tmp_path / "s1" / "atom_sasa.npy")
+    assert s.dtype == np.float32 and len(s) == 500 and np.all(np.diff(s) > 0)
+    assert np.array_equal(s, np.load(tmp_path / "s2" / "atom_sasa.npy"))
+    assert len(np.load(tmp_path / "s1" / "residue_sasa.npy")) == 50

@@ -150,7 +150,7 @@ def test_two_ranks_share_one_gpu():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
                         "--device", "0", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--h2h-steps", "2",
                         "--two-steps", "2", "--config5-steps", "0", "--files", "0", "--per-call-seconds", "0", "--weak-steps", "2",
-                        "--structures", "96", "--verify-shards"], capture_output=True, text=True, env=env,
+                        "--structures", "96", "--verify-shards", "--full"], capture_output=True, text=True, env=env,
                        timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

@@ -1,6 +1,7 @@
 #!/bin/bash
 # rocprofv3 --kernel-trace --stats of a short bench run (any bench.py arguments), the engine's kernels with calls and
 # average / minimum / maximum duration.  usage (GPU box): tools/kernel_stats.sh [bench.py args]
+set -- --full "$@"  # (the ids_as_hashes leg printed at the end runs under --full)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/kstats; mkdir -p gpurun_out
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/kstats -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --h2h-steps 0 --two-steps 0 --config5-steps 0 --files 0 --per-call-seconds 0 --real-steps 0 "$@" > gpurun_out/kstats.log 2>&1

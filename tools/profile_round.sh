@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (on the GPU box, from the repo root): tools/profile_round.sh <tag>
 # Everything profiles/ holds for one build, written under gpurun_out/<tag>/:
-#   bench.json                 default `python bench.py` line (with the CPU baseline leg)
+#   bench.json                 `python bench.py --full` line (with the CPU baseline leg)
 #   kernel_stats.csv           rocprofv3 --kernel-trace --stats of `bench.py --steps 20 --warmup 3 --cpu-seconds 0`
 #   bench_under_rocprof.json   the bench line of that profiled run
 #   pmc.txt                    PMC summaries of the occlusion kernel (separate passes, no tracing): instruction mix, waits,
@@ -11,13 +11,13 @@
 #                              host batches against one call after the other
 #   pmc_uniform1m.txt          the same instruction-mix, matrix-pipe and GRBM_GUI_ACTIVE passes for the 1M-atom / 960-point dispatch
 #   bench_uniform1m.json, single_and_pcie.json, files_mode.json, files_mode_1500.json, files_mode_cif.json, bench_shard_of_8.json,
-#   two_in_flight.txt, bench_run2.json (a second default run at the end), per_call_combined.txt (the drop-in call alone and with call
+#   two_in_flight.txt, bench_run2.json (a second --full run at the end), per_call_combined.txt (the drop-in call alone and with call
 #   combining), files_end_to_end.json / _cif.json (4 363 files in -> 4 363 JSON files out)
 tag=${1:-round}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-python3 bench.py > $out/bench.log 2>&1; tail -1 $out/bench.log > $out/bench.json
+python3 bench.py --full > $out/bench.log 2>&1; tail -1 $out/bench.log > $out/bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --steps 20 --warmup 3 --cpu-seconds 0 --h2h-steps 0 --two-steps 0 --config5-steps 0 --files 0 --per-call-seconds 0 --real-steps 0 --hashed-ids-steps 0 > $out/trace.log 2>&1
 cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 grep '^{"metric"' $out/trace.log | tail -1 > $out/bench_under_rocprof.json
@@ -37,14 +37,14 @@ rocprofv3 --pmc SQ_WAVES SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COE
 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $out/pmcu_g -- python3 bench.py --workload uniform1m --steps 1 --warmup 0 --cpu-seconds 0 --h2h-steps 0 --two-steps 0 --hashed-ids-steps 0 > /dev/null 2>&1
 python3 tools/pmc_summary.py "$out/pmcu_*/**/*counter_collection.csv" > $out/pmc_uniform1m.txt 2>&1
 rm -rf $out/pmcu_a $out/pmcu_c $out/pmcu_g
-python3 bench.py --workload uniform1m --cpu-seconds 0 --h2h-steps 0 --two-steps 0 --hashed-ids-steps 0 > $out/u1m.log 2>&1; tail -1 $out/u1m.log > $out/bench_uniform1m.json
+python3 bench.py --full --workload uniform1m --cpu-seconds 0 --h2h-steps 0 --two-steps 0 --hashed-ids-steps 0 > $out/u1m.log 2>&1; tail -1 $out/u1m.log > $out/bench_uniform1m.json
 python3 tools/bench_single.py 2>/dev/null > $out/single_and_pcie.json
 python3 tools/bench_files.py --files 4363 --repeat 3 --calls 4 > $out/files.log 2>&1; tail -1 $out/files.log > $out/files_mode.json
 python3 tools/bench_files.py --files 1500 --repeat 3 --calls 4 > $out/files1500.log 2>&1; tail -1 $out/files1500.log > $out/files_mode_1500.json
 python3 tools/bench_files.py --files 4363 --repeat 3 --calls 4 --format cif > $out/files_cif.log 2>&1; tail -1 $out/files_cif.log > $out/files_mode_cif.json
-python3 bench.py --shard-of 8 > $out/shard8.log 2>&1; tail -1 $out/shard8.log > $out/bench_shard_of_8.json
+python3 bench.py --full --shard-of 8 > $out/shard8.log 2>&1; tail -1 $out/shard8.log > $out/bench_shard_of_8.json
 python3 tools/bench_two_in_flight.py 1 8 2>&1 | grep "^shard" > $out/two_in_flight.txt
-python3 bench.py > $out/bench2.log 2>&1; tail -1 $out/bench2.log > $out/bench_run2.json
+python3 bench.py --full > $out/bench2.log 2>&1; tail -1 $out/bench2.log > $out/bench_run2.json
 tools/microbench_clock > $out/microbench_clock.txt 2>&1
 H2H_REPS=5 python3 tools/bench_h2h_stream.py --api 12 2>/dev/null | tail -3 > $out/h2h_stream.txt
 H2H_SORTED=1 python3 tools/bench_h2h.py 8 2>/dev/null | tail -1 >> $out/h2h_stream.txt
