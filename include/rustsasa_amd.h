@@ -34,7 +34,9 @@ extern "C" {
  *    rsasa_context_ids_dropped added;
  * 4: rsasa_context_set_call_combining, rsasa_call_combining_stats, rsasa_context_ids_kept added; rsasa_host_batch_enqueue with eight batches
  *    queued returns RSASA_ERR_QUEUE_FULL at once (it used to wait for the oldest batch and then fail);
- * nothing else changed, nothing removed. */
+ * nothing else changed, nothing removed.
+ * Additive under 4 (callers detect them by symbol): rsasa_neighbor_t, rsasa_precompute_neighbors,
+ * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -45,7 +47,9 @@ typedef enum rsasa_status {
     RSASA_ERR_OUT_OF_MEMORY = -4,
     RSASA_ERR_GRID_TOO_LARGE = -5,   /* a structure's cell grid exceeds 2^31 cells (coordinates too sparse) */
     RSASA_ERR_INTERNAL = -6,
-    RSASA_ERR_QUEUE_FULL = -7        /* rsasa_host_batch_enqueue: eight batches are queued and not yet waited for */
+    RSASA_ERR_QUEUE_FULL = -7,       /* rsasa_host_batch_enqueue: eight batches are queued and not yet waited for */
+    RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*: out_entries is NULL or holds fewer entries than
+                                        out_offsets[n] (which has been written) */
 } rsasa_status;
 
 /* Mirrors `Atom` (reference src/structures/atomic.rs:13-24) without the
@@ -270,6 +274,78 @@ int rsasa_calculate_sasa_trajectory(rsasa_context_t *ctx, const float *xyz, size
  * (src/options.rs:216,308,392,404). */
 int rsasa_segment_sums(rsasa_context_t *ctx, const float *values, size_t n_values,
                        const uint32_t *offsets, size_t n_segments, float *out);
+
+/* ---- neighbour lists ---------------------------------------------------- */
+
+/* The reference's neighbour search as a product of its own:
+ *
+ *     pub fn precompute_neighbors(atoms: &[Atom], active_indices: &[usize],
+ *                                 probe_radius: f32, max_radii: f32) -> Vec<Vec<NeighborData>>
+ *                                                     (reference src/lib.rs:69-84)
+ *
+ * built by SpatialGrid::new / build_all_neighbor_lists and sorted by
+ * sort_neighbors_by_distance (src/structures/spatial_grid.rs:28-50,195-465).
+ * The lists are returned in CSR form: the list of active atom a is
+ * out_entries[out_offsets[a] .. out_offsets[a + 1]).  Atom j is in atom i's
+ * list exactly when j is active, j != i, id_j != id_i, d^2 <= (2 max_r + 2p)^2
+ * and d^2 <= (r_i + max_r + 2p)^2, d^2 = dx*dx + dy*dy + dz*dz (not fused)
+ * (spatial_grid.rs:300-341).  Entries hold the neighbour's ORIGINAL index and
+ * threshold_squared = (r_j + p) * (r_j + p).
+ *
+ * Order: each list is sorted ascending by (d^2, idx), d^2 the centre-relative
+ * key the reference sorts on (spatial_grid.rs:452-462) - one of the orders its
+ * sort_unstable_by may give, and a deterministic one.
+ *
+ * max_radius is taken as given, as by the reference (grid cell size
+ * probe + max_radius, both distance tests); NaN means fold(0, max) of the
+ * active atoms' radii (lib.rs:259-262).  The "Non-finite input" paragraph
+ * above holds: a NaN coordinate is nobody's neighbour and has an empty list; a
+ * NaN radius gives that atom an empty list and a NaN threshold in the lists of
+ * others; an infinite coordinate returns RSASA_ERR_GRID_TOO_LARGE.
+ *
+ * Sizing: out_offsets is always written (on success and on
+ * RSASA_ERR_BUFFER_TOO_SMALL).  If out_entries is NULL or entries_capacity <
+ * out_offsets[n], nothing else is written and RSASA_ERR_BUFFER_TOO_SMALL is
+ * returned: call once to size, allocate, call again.
+ *
+ * Both calls are synchronous and run on the GPU in a workspace of their own
+ * on the context's first stream: device batches in flight on the context
+ * (rsasa_batch_enqueue) are neither waited for nor disturbed - they keep
+ * their results and errors for rsasa_batch_wait - and streams of host
+ * batches run on contexts of their own. */
+
+/* NeighborData (reference src/structures/atomic.rs:5-10), repr(C), 8 bytes. */
+typedef struct rsasa_neighbor {
+    float threshold_squared;
+    uint32_t idx;
+} rsasa_neighbor_t;
+
+/* precompute_neighbors (reference src/lib.rs:69-84) for one structure.
+ * id: nullable (all atoms distinct).  active_indices: nullable (every atom,
+ * in order); else n_active distinct indices below n_atoms (otherwise
+ * RSASA_ERR_INVALID_ARGUMENT).  Only active atoms are binned and bounded
+ * (spatial_grid.rs:52-90); lists are indexed by active position, idx is the
+ * original index.  out_offsets: [n_active + 1]. */
+int rsasa_precompute_neighbors(rsasa_context_t *ctx,
+                               const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, size_t n_atoms,
+                               const uint32_t *active_indices, size_t n_active,
+                               float probe_radius, float max_radius,
+                               uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                               size_t entries_capacity);
+
+/* Directory-mode form: n_structures independent structures, one grid each
+ * (as that many rsasa_precompute_neighbors calls without active_indices).
+ * idx is the index WITHIN the structure; out_offsets is batch-global
+ * [structure_offsets[n_structures] + 1].  A NaN max_radius is each
+ * structure's own maximum. */
+int rsasa_precompute_neighbors_batch(rsasa_context_t *ctx,
+                                     const float *x, const float *y, const float *z, const float *radius,
+                                     const uint64_t *id,
+                                     const uint32_t *structure_offsets, size_t n_structures,
+                                     float probe_radius, float max_radius,
+                                     uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                                     size_t entries_capacity);
 
 /* ---- measurement ------------------------------------------------------- */
 

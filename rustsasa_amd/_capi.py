@@ -22,11 +22,16 @@ RSASA_ERR_OUT_OF_MEMORY = -4
 RSASA_ERR_GRID_TOO_LARGE = -5
 RSASA_ERR_INTERNAL = -6
 RSASA_ERR_QUEUE_FULL = -7
+RSASA_ERR_BUFFER_TOO_SMALL = -8
 
 # numpy image of rsasa_atom_t (mirrors `Atom`, reference src/structures/atomic.rs:13-24)
 ATOM_DTYPE = np.dtype([("position", np.float32, (3,)), ("radius", np.float32), ("id", np.uint64)],
                       align=True)
 assert ATOM_DTYPE.itemsize == 24
+
+# numpy image of rsasa_neighbor_t (mirrors `NeighborData`, reference src/structures/atomic.rs:5-10)
+NEIGHBOR_DTYPE = np.dtype([("threshold_squared", "<f4"), ("idx", "<u4")])
+assert NEIGHBOR_DTYPE.itemsize == 8
 
 
 class RsasaError(RuntimeError):
@@ -94,6 +99,10 @@ SYMBOLS = {
     "rsasa_context_ids_kept": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
     "rsasa_context_set_call_combining": (C.c_int, [_vp, C.c_int]),
     "rsasa_call_combining_stats": (C.c_int, [C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "rsasa_precompute_neighbors": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t,
+                                             C.c_float, C.c_float, _vp, _vp, C.c_size_t]),
+    "rsasa_precompute_neighbors_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                                   C.c_float, C.c_float, _vp, _vp, C.c_size_t]),
     "rsasa_sphere_points": (C.c_int, [C.c_size_t, _vp, _vp, _vp]),
 }
 

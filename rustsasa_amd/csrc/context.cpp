@@ -642,6 +642,7 @@ const char *rsasa_status_string(int status)
     case RSASA_ERR_GRID_TOO_LARGE: return "cell grid too large";
     case RSASA_ERR_INTERNAL: return "internal error";
     case RSASA_ERR_QUEUE_FULL: return "host batch queue full";
+    case RSASA_ERR_BUFFER_TOO_SMALL: return "output buffer too small (the offsets give the size needed)";
     default: return "unknown status";
     }
 }
@@ -782,6 +783,7 @@ int rsasa_context_destroy(rsasa_context_t *ctx)
                             &ctx->tr_id, &ctx->tr_res})
         release(*b);
     for (DeviceBuffer &b : ctx->in_pack) release(b);
+    neighbors_release(ctx);
     for (auto &m : ctx->more)
         for (DeviceBuffer *b : {&m.x, &m.y, &m.z, &m.r, &m.id, &m.res, &m.atom_sasa, &m.out_res}) release(*b);
     // (the coding pool is the device's, shared by its contexts: it stays)

@@ -161,6 +161,45 @@ struct BatchView {
     // atom to the general kernel, and launch_occlusion then does NOT launch that kernel - the caller looks at
     // the flag after the stream has drained and calls launch_occlusion_deferred if it is set (it rarely is).
     uint32_t *defer_flag;
+    // rsasa_precompute_neighbors*: the max_radius the caller gave (precompute_neighbors takes it as given, reference
+    // src/lib.rs:69-84): make_grid builds every structure's grid and search radii from it instead of StructAcc::max_r.
+    // NaN (the default): no override - the SASA path never sets it.
+    float max_r_override = __builtin_nanf("");
+};
+
+// ---- neighbour lists (neighbors.hip, rsasa_precompute_neighbors*) ----
+// What the host reads back after the count and scan kernels, and the cursors of the fill kernel.
+struct NbInfo {
+    unsigned long long total;          // entries of all lists (offsets[n])
+    unsigned long long max_k;          // the longest list
+    unsigned long long spill_entries;  // entries of the lists longer than the fill kernel's LDS staging
+    unsigned long long spill_atoms;    // number of such lists
+    unsigned long long spill_cursor;   // k_neighbor_fill: entries of NbArgs::spill handed out
+    unsigned long long spill_recs;     // k_neighbor_fill: records of NbArgs::spill_recs written
+    unsigned long long mismatch;       // nonzero: the fill pass accepted a different number of candidates than the count pass
+    unsigned long long pad;
+};
+static_assert(sizeof(NbInfo) == 64, "NbInfo layout");
+struct NbKey {                 // a staged candidate of a long list: (float bits of d^2) << 32 | idx, and its threshold
+    unsigned long long key;
+    float thr;
+    uint32_t pad;
+};
+struct NbSpillRec {            // a long list: its entries at out[off ..), its keys at spill[base ..), k of them
+    unsigned long long off, base;
+    uint32_t k, pad;
+};
+struct NbArgs {
+    BatchView b;
+    uint32_t *counts;                // [n_atoms] list length of input atom i
+    unsigned long long *offsets;     // [n_atoms + 1] exclusive scan of counts
+    unsigned long long *parts;       // scan: 4 entries per workgroup of the scan
+    NbInfo *info;
+    const uint32_t *idx_map;         // nullable: input atom -> the index written to the entries (active_indices);
+                                     // null: the index within the structure
+    uint2 *out;                      // (threshold_squared bits, idx) = rsasa_neighbor_t
+    NbKey *spill;
+    NbSpillRec *spill_recs;
 };
 
 // Grid and status of a one-structure batch, computed by the host and handed to k_sort_window<true> as
@@ -219,6 +258,9 @@ bool occlusion_uses_mx(const OcclusionTuning &tune, const Lattice &lat, uint32_t
 // The general kernel over the atoms the straight-line kernel deferred (see BatchView::defer_flag).
 void launch_occlusion_deferred(const BatchView &b, const Lattice &lat, hipStream_t stream);
 void launch_residue_sums(const BatchView &b, hipStream_t stream);
+// Neighbour lists (neighbors.hip) on a binned batch: counts, offsets and NbInfo; then the entries.
+void launch_neighbor_count(const NbArgs &a, hipStream_t stream);
+void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
 // Pinned 24-byte atom records (x, y, z, r, id) -> device columns, and `hdr_bytes` of header beside them (combine.cpp).
 void launch_unpack_atoms(const void *records, uint32_t n_atoms, float *x, float *y, float *z, float *r, uint64_t *id,
                          const void *hdr_src, void *hdr_dst, uint32_t hdr_bytes, hipStream_t stream);

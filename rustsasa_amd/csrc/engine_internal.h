@@ -391,6 +391,12 @@ struct rsasa_context {
     size_t stream_sub_batches = 0; // a worker context of a stream of host batches: most sub-batches of a call (0: the default)
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
+    // rsasa_precompute_neighbors*: a workspace of their own (neighbors.cpp) - device batches in flight in ws[0] / ws[1] are
+    // neither waited for nor disturbed; the calls queue their work on `stream` behind whatever it holds
+    Workspace nb_ws;
+    DeviceBuffer nb_x, nb_y, nb_z, nb_r, nb_id, nb_map, nb_counts, nb_offsets, nb_parts, nb_info, nb_entries, nb_spill, nb_recs;
+    void *nb_host = nullptr;       // pinned: the BatchStatus and NbInfo of the last neighbour call
+    uint64_t nb_cell_capacity = 0;
 };
 
 namespace rsasa {
@@ -498,6 +504,7 @@ int wait_oldest(rsasa_context *ctx);
 int wait_pending(rsasa_context *ctx);
 int resolve_ctx(rsasa_context *&ctx);
 int context_create(int device, int own_queues, rsasa_context_t **out_ctx);  // own_queues: rsasa_context::own_queues
+void neighbors_release(rsasa_context *ctx);  // frees the neighbour calls' workspace (rsasa_context_destroy)
 int batch_enqueue(rsasa_context *ctx, const rsasa_device_batch_t *batch, float probe_radius, size_t n_points, void *hip_stream,
                   bool ids_needed_known);  // rsasa_batch_enqueue with the host's verdict on the ids
 

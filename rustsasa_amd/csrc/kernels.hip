@@ -206,10 +206,11 @@ __global__ __launch_bounds__(256) void k_ids_segments(BatchView b)
 }
 
 // SpatialGrid::new parameters (spatial_grid.rs:35-44 with cell_size from lib.rs:76).
-__device__ __forceinline__ StructGrid make_grid(const StructAcc &a, float probe, bool &bad, bool &too_large)
+// max_r_override: BatchView::max_r_override (NaN: the structure's own maximum radius).
+__device__ __forceinline__ StructGrid make_grid(const StructAcc &a, float probe, float max_r_override, bool &bad, bool &too_large)
 {
     StructGrid g = {};
-    float max_r = ord2f(a.max_r);
+    float max_r = max_r_override == max_r_override ? max_r_override : ord2f(a.max_r);
     float cell = probe + max_r;                                    // lib.rs:76
     float inv = 1.0f / cell;                                       // spatial_grid.rs:36
     float mn[3] = {ord2f(a.min_x) - cell, ord2f(a.min_y) - cell, ord2f(a.min_z) - cell};
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(256) void k_grid_params(BatchView b)
     unsigned long long n_cells = 0;
     if (s < b.n_structures) {
         bool bad = false, too_large = false;
-        const StructGrid g = make_grid(b.acc[s], b.probe, bad, too_large);
+        const StructGrid g = make_grid(b.acc[s], b.probe, b.max_r_override, bad, too_large);
         b.grids[s] = g;  // cell_base / sorted_base follow in k_grid_bases
         if (bad) b.status->bad_input = 1u;
         if (too_large) b.status->grid_too_large = 1u;

@@ -1,0 +1,228 @@
+// Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h): the
+// batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws), then
+// neighbors.hip counts, scans and fills the lists.  Host code only.
+#include "engine_internal.h"
+
+namespace {
+
+using namespace rsasa;
+
+struct NbHost {  // the pinned block the device's verdicts come back in
+    BatchStatus status;
+    NbInfo info;
+};
+
+// One run over columns already in host memory: S structures, N atoms.  idx_map (host, nullable): input atom -> the
+// index written to the entries.
+int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *so, size_t S, size_t N, const uint32_t *idx_map, float probe, float max_r,
+           uint64_t *out_offsets, rsasa_neighbor_t *out_entries, size_t cap)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    rsasa_context::Workspace &W = ctx->nb_ws;
+    hipStream_t st = ctx->stream;
+
+    std::vector<Segment> segs;
+    bool has_tail = false;
+    for (size_t s = 0; s < S; s++) {
+        const uint32_t b = so[s], e = so[s + 1];
+        has_tail |= e - b >= kLdsMaxAtoms;
+        for (uint32_t a = b; a < e; a += kSegmentAtoms)
+            segs.push_back(Segment{(uint32_t)s, a, std::min(e, a + kSegmentAtoms), a != b ? 1u : 0u});
+    }
+    const bool has_id = id != nullptr;
+    if (!ctx->nb_host) RS_HIP(ctx, hipHostMalloc(&ctx->nb_host, sizeof(NbHost), hipHostMallocDefault));
+    NbHost *h = static_cast<NbHost *>(ctx->nb_host);
+
+    if ((rc = reserve(ctx, ctx->nb_x, N * 4)) || (rc = reserve(ctx, ctx->nb_y, N * 4)) || (rc = reserve(ctx, ctx->nb_z, N * 4)) ||
+        (rc = reserve(ctx, ctx->nb_r, N * 4)) || (has_id && (rc = reserve(ctx, ctx->nb_id, N * 8))) ||
+        (idx_map && (rc = reserve(ctx, ctx->nb_map, N * 4))))
+        return rc;
+    RS_HIP(ctx, hipMemcpyAsync(ctx->nb_x.p, x, N * 4, hipMemcpyHostToDevice, st));
+    RS_HIP(ctx, hipMemcpyAsync(ctx->nb_y.p, y, N * 4, hipMemcpyHostToDevice, st));
+    RS_HIP(ctx, hipMemcpyAsync(ctx->nb_z.p, z, N * 4, hipMemcpyHostToDevice, st));
+    RS_HIP(ctx, hipMemcpyAsync(ctx->nb_r.p, r, N * 4, hipMemcpyHostToDevice, st));
+    if (has_id) RS_HIP(ctx, hipMemcpyAsync(ctx->nb_id.p, id, N * 8, hipMemcpyHostToDevice, st));
+    if (idx_map) RS_HIP(ctx, hipMemcpyAsync(ctx->nb_map.p, idx_map, N * 4, hipMemcpyHostToDevice, st));
+
+    // ---- the grid (as enqueue_batch builds it, without the id check: every id takes part), grown until the cells fit
+    if (ctx->nb_cell_capacity == 0) ctx->nb_cell_capacity = std::max<uint64_t>(1u << 16, 20ull * N + 512ull * S);
+    BatchView v{};
+    for (int attempt = 0;; attempt++) {
+        ctx->nb_cell_capacity = std::min<uint64_t>(ctx->nb_cell_capacity, 0xFFFFFFF0ull);
+        const uint64_t window_capacity = std::min<uint64_t>(2 * ctx->nb_cell_capacity / kWindowCells + S + 1, 0x7FFFFFFFull);
+        if ((rc = reserve(ctx, W.segments, std::max<size_t>(segs.size(), 1) * sizeof(Segment))) ||
+            (rc = reserve(ctx, W.acc, S * sizeof(StructAcc))) || (rc = reserve(ctx, W.grids, S * sizeof(StructGrid))) ||
+            (rc = reserve(ctx, W.grid_sums, (S + 255) / 256 * 32)) || (rc = reserve(ctx, W.sid_sorted, N * 4)) ||
+            (has_tail && (rc = reserve(ctx, W.cell_of, N * 4))) || (rc = reserve(ctx, W.rank_of, N * 4)) ||
+            (rc = reserve(ctx, W.cells, (size_t)(ctx->nb_cell_capacity + 1 + 3) * 4)) ||
+            (rc = reserve(ctx, W.windows, (size_t)window_capacity * sizeof(uint4))) ||
+            (rc = reserve(ctx, W.scan_sums, kScanBlocks * 4)) || (rc = reserve(ctx, W.sorted_xyzr, N * 16)) ||
+            (rc = reserve(ctx, W.sorted_orig, N * 4)) || (has_id && (rc = reserve(ctx, W.sorted_id32, N * 4))) ||
+            (rc = reserve(ctx, W.status, sizeof(BatchStatus))))
+            return rc;
+        if (!segs.empty())
+            RS_HIP(ctx, hipMemcpyAsync(W.segments.p, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice, st));
+        v = BatchView{};
+        v.x = (const float *)ctx->nb_x.p; v.y = (const float *)ctx->nb_y.p; v.z = (const float *)ctx->nb_z.p;
+        v.radius = (const float *)ctx->nb_r.p;
+        v.id = has_id ? (const uint64_t *)ctx->nb_id.p : nullptr;
+        v.n_atoms = (uint32_t)N; v.n_structures = (uint32_t)S; v.n_segments = (uint32_t)segs.size();
+        v.probe = probe;
+        v.max_r_override = max_r;
+        v.segments = (const Segment *)W.segments.p;
+        v.acc = (StructAcc *)W.acc.p;
+        v.grids = (StructGrid *)W.grids.p;
+        v.grid_sums = (GridSums *)W.grid_sums.p;
+        v.sid_sorted = (uint32_t *)W.sid_sorted.p;
+        v.cell_of = (uint32_t *)W.cell_of.p;
+        v.rank_of = (uint32_t *)W.rank_of.p;
+        v.cells = (uint32_t *)W.cells.p;
+        v.cell_capacity = ctx->nb_cell_capacity;
+        v.windows = (uint4 *)W.windows.p;
+        v.window_capacity = (uint32_t)window_capacity;
+        v.scan_block_sums = (uint32_t *)W.scan_sums.p;
+        v.sorted_xyzr = (float4 *)W.sorted_xyzr.p;
+        v.sorted_orig = (uint32_t *)W.sorted_orig.p;
+        v.sorted_id32 = has_id ? (uint32_t *)W.sorted_id32.p : nullptr;
+        v.status = (BatchStatus *)W.status.p;
+        launch_grid_prepare(v, st);
+        launch_sort_lds(v, st);
+        if (has_tail) launch_sort_tail(v, st);
+        RS_HIP(ctx, hipMemcpyAsync(&h->status, W.status.p, sizeof(BatchStatus), hipMemcpyDeviceToHost, st));
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, hipStreamSynchronize(st));
+        const BatchStatus stt = h->status;
+        if (stt.grid_too_large)
+            return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "a structure's cell grid exceeds 2^31 cells (coordinates too sparse)");
+        if (stt.bad_input)
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "probe_radius + max radius must be a positive finite number");
+        if (!stt.overflow) break;
+        if (stt.total_cells >= 0xFFFFFFF0ull || attempt >= 3)
+            return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "batch needs more than 2^32 grid cells; split it");
+        ctx->nb_cell_capacity = stt.total_cells + stt.total_cells / 8 + 1024;  // (as wait_one: grow, run again)
+    }
+
+    // ---- counts, offsets
+    NbArgs a{};
+    a.b = v;
+    if ((rc = reserve(ctx, ctx->nb_counts, N * 4)) || (rc = reserve(ctx, ctx->nb_offsets, (N + 1) * 8)) ||
+        (rc = reserve(ctx, ctx->nb_parts, 4 * 1024 * 8)) || (rc = reserve(ctx, ctx->nb_info, sizeof(NbInfo))))
+        return rc;
+    a.counts = (uint32_t *)ctx->nb_counts.p;
+    a.offsets = (unsigned long long *)ctx->nb_offsets.p;
+    a.parts = (unsigned long long *)ctx->nb_parts.p;
+    a.info = (NbInfo *)ctx->nb_info.p;
+    a.idx_map = idx_map ? (const uint32_t *)ctx->nb_map.p : nullptr;
+    RS_HIP(ctx, hipMemsetAsync(a.info, 0, sizeof(NbInfo), st));
+    launch_neighbor_count(a, st);
+    RS_HIP(ctx, hipMemcpyAsync(&h->info, a.info, sizeof(NbInfo), hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipMemcpyAsync(out_offsets, a.offsets, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    const NbInfo info = h->info;
+    if (info.total != out_offsets[N]) return fail(ctx, RSASA_ERR_INTERNAL, "neighbour offsets disagree with their total");
+    if (!out_entries || cap < info.total)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_entries holds fewer entries than out_offsets[n]");
+    if (info.total == 0) return RSASA_OK;
+
+    // ---- entries
+    if ((rc = reserve(ctx, ctx->nb_entries, info.total * 8)) ||
+        (info.spill_atoms && ((rc = reserve(ctx, ctx->nb_spill, info.spill_entries * sizeof(NbKey))) ||
+                              (rc = reserve(ctx, ctx->nb_recs, info.spill_atoms * sizeof(NbSpillRec))))))
+        return rc;
+    a.out = (uint2 *)ctx->nb_entries.p;
+    a.spill = info.spill_atoms ? (NbKey *)ctx->nb_spill.p : nullptr;
+    a.spill_recs = info.spill_atoms ? (NbSpillRec *)ctx->nb_recs.p : nullptr;
+    launch_neighbor_fill(a, info.spill_atoms, st);
+    RS_HIP(ctx, hipMemcpyAsync(&h->info, a.info, sizeof(NbInfo), hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    if (h->info.mismatch || h->info.spill_cursor != info.spill_entries || h->info.spill_recs != info.spill_atoms)
+        return fail(ctx, RSASA_ERR_INTERNAL, "the neighbour fill pass disagrees with its count pass");
+    RS_HIP(ctx, hipMemcpyAsync(out_entries, a.out, info.total * 8, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+}  // namespace
+
+namespace rsasa {
+
+void neighbors_release(rsasa_context *ctx)
+{
+    rsasa_context::Workspace &W = ctx->nb_ws;
+    for (DeviceBuffer *b : {&W.segments, &W.acc, &W.grids, &W.grid_sums, &W.sid_sorted, &W.deferred_list, &W.cell_of, &W.rank_of,
+                            &W.cells, &W.windows, &W.scan_sums, &W.sorted_xyzr, &W.sorted_orig, &W.sorted_id, &W.sorted_id32,
+                            &W.status, &W.atom_sasa, &W.claim, &W.ids_seg, &ctx->nb_x, &ctx->nb_y, &ctx->nb_z, &ctx->nb_r,
+                            &ctx->nb_id, &ctx->nb_map, &ctx->nb_counts, &ctx->nb_offsets, &ctx->nb_parts, &ctx->nb_info,
+                            &ctx->nb_entries, &ctx->nb_spill, &ctx->nb_recs})
+        release(*b);
+    if (ctx->nb_host) (void)hipHostFree(ctx->nb_host);
+    ctx->nb_host = nullptr;
+}
+
+}  // namespace rsasa
+
+extern "C" {
+
+int rsasa_precompute_neighbors(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, size_t n_atoms, const uint32_t *active_indices, size_t n_active,
+                               float probe_radius, float max_radius, uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                               size_t entries_capacity)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    const size_t n = active_indices ? n_active : n_atoms;
+    if (!out_offsets || (n_atoms && (!x || !y || !z || !radius)) || (n_active && !active_indices))
+        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_atoms >= 0x7FFFFFFFull || n >= 0x7FFFFFFFull)
+        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    if (!active_indices) {
+        const uint32_t so[2] = {0u, (uint32_t)n_atoms};
+        return nb_run(ctx, x, y, z, radius, id, so, 1, n_atoms, nullptr, probe_radius, max_radius, out_offsets, out_entries,
+                      entries_capacity);
+    }
+    // only the active atoms are binned and bounded (spatial_grid.rs:52-90, calculate_bounds): gather them, map idx back
+    std::vector<uint8_t> seen(n_atoms, 0);
+    std::vector<float> gx(n), gy(n), gz(n), gr(n);
+    std::vector<uint64_t> gid(id ? n : 0);
+    for (size_t k = 0; k < n; k++) {
+        const uint32_t i = active_indices[k];
+        if (i >= n_atoms || seen[i]) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "active_indices must be distinct and below n_atoms");
+        seen[i] = 1;
+        gx[k] = x[i]; gy[k] = y[i]; gz[k] = z[i]; gr[k] = radius[i];
+        if (id) gid[k] = id[i];
+    }
+    const uint32_t so[2] = {0u, (uint32_t)n};
+    return nb_run(ctx, gx.data(), gy.data(), gz.data(), gr.data(), id ? gid.data() : nullptr, so, 1, n, active_indices,
+                  probe_radius, max_radius, out_offsets, out_entries, entries_capacity);
+}
+
+int rsasa_precompute_neighbors_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                                     const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures,
+                                     float probe_radius, float max_radius, uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                                     size_t entries_capacity)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!structure_offsets || !out_offsets) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_structures >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "too many structures");
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1])
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (n_structures && structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets[0] must be 0");
+    if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    if (N && (!x || !y || !z || !radius)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    return nb_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, nullptr, probe_radius, max_radius, out_offsets,
+                  out_entries, entries_capacity);
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import ATOM_DTYPE, DeviceBatch, RsasaError, Timings, check, ptr
+from ._capi import ATOM_DTYPE, NEIGHBOR_DTYPE, DeviceBatch, RsasaError, Timings, check, ptr
 
 
 def device_count() -> int:
@@ -196,6 +196,60 @@ class Context:
         while self._host_keepalive:
             self.host_batch_wait()
 
+    # ---- neighbour lists (precompute_neighbors, reference src/lib.rs:69-84) --
+    def _neighbor_call(self, call, n_lists: int):
+        """Runs `call(offsets, entries, capacity)` with a guessed capacity, and once more at the size the offsets give
+        when that was too small; returns (offsets uint64[n_lists + 1], entries NEIGHBOR_DTYPE[total])."""
+        offsets = np.zeros(n_lists + 1, np.uint64)
+        entries = np.empty(64 * n_lists, NEIGHBOR_DTYPE)
+        rc = call(offsets, entries, entries.shape[0])
+        if rc == _capi.RSASA_ERR_BUFFER_TOO_SMALL:
+            entries = np.empty(int(offsets[-1]), NEIGHBOR_DTYPE)
+            rc = call(offsets, entries, entries.shape[0])
+        self._check(rc)
+        return offsets, entries[:int(offsets[-1])]
+
+    def precompute_neighbors(self, x, y, z, radius, ids=None, probe_radius: float = 1.4,
+                             max_radius: Optional[float] = None, active_indices=None):
+        """rsasa_precompute_neighbors: the lists of the active atoms (all atoms when active_indices is None) in CSR form,
+        (offsets uint64[n_active + 1], entries NEIGHBOR_DTYPE[total]); each list sorted by (d^2, idx).  max_radius None:
+        the largest active radius (NaN radii skipped)."""
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        act = None
+        if active_indices is not None:
+            act = np.ascontiguousarray(active_indices, dtype=np.uint32)
+            if act.ndim != 1:
+                raise ValueError("active_indices must be a 1-D array")
+        n_lists = x.shape[0] if act is None else act.shape[0]
+        mr = float("nan") if max_radius is None else float(max_radius)
+
+        def call(offsets, entries, cap):
+            return self._lib.rsasa_precompute_neighbors(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], ptr(act),
+                0 if act is None else act.shape[0], probe_radius, mr, ptr(offsets), ptr(entries), cap)
+        return self._neighbor_call(call, n_lists)
+
+    def precompute_neighbors_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
+                                   max_radius: Optional[float] = None):
+        """rsasa_precompute_neighbors_batch: one grid per structure; (offsets uint64[n_atoms + 1] over the whole
+        batch, entries NEIGHBOR_DTYPE[total]) with idx the index within the structure."""
+        so = _offsets("structure_offsets", structure_offsets)
+        n_struct = so.shape[0] - 1
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
+        mr = float("nan") if max_radius is None else float(max_radius)
+
+        def call(offsets, entries, cap):
+            return self._lib.rsasa_precompute_neighbors_batch(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, mr,
+                ptr(offsets), ptr(entries), cap)
+        return self._neighbor_call(call, x.shape[0])
+
+    def neighbor_lists(self, x, y, z, radius, ids=None, probe_radius: float = 1.4,
+                       max_radius: Optional[float] = None, active_indices=None):
+        """precompute_neighbors as a list of per-atom NEIGHBOR_DTYPE arrays (one per active atom, like Vec<Vec<NeighborData>>)."""
+        offsets, entries = self.precompute_neighbors(x, y, z, radius, ids, probe_radius, max_radius, active_indices)
+        return [entries[int(offsets[i]):int(offsets[i + 1])] for i in range(offsets.shape[0] - 1)]
+
     # ---- MD trajectory: one topology, many frames --------------------------
     def calculate_sasa_trajectory(self, xyz, radius, ids=None, probe_radius: float = 1.4,
                                   n_points: int = 100, residue_offsets=None, want_atoms: bool = True):
@@ -309,4 +363,4 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
     return a
 
 
-__all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "ATOM_DTYPE"]
+__all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
