@@ -8,11 +8,10 @@ import pytest
 import bench_workloads as bw
 import structio as sio
 import tie_cases as tc
+from nb_helpers import PROBE, assert_same, csr, fold_max, oracle_csr, protor, sorted_lists
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
-
-PROBE = 1.4
 
 
 @pytest.fixture(scope="module")
@@ -21,59 +20,6 @@ def ctx():
     c = rustsasa_amd.Context(0)
     yield c
     c.close()
-
-
-def _f32(a):
-    return np.ascontiguousarray(a, dtype=np.float32)
-
-
-def fold_max(r):
-    """fold(0.0, f32::max) of the radii (lib.rs:259-262): NaN radii are skipped."""
-    r = _f32(r)
-    r = r[~np.isnan(r)]
-    return float(max(np.float32(0.0), np.max(r, initial=np.float32(0.0))))
-
-
-def sorted_lists(lists, x, y, z, centre_of=None):
-    """Each list re-sorted by (d^2, idx), d^2 the centre-relative key of spatial_grid.rs:452-462 in f32."""
-    x, y, z = _f32(x), _f32(y), _f32(z)
-    out = []
-    for a, lst in enumerate(lists):
-        c = a if centre_of is None else centre_of[a]
-        j = lst["idx"].astype(np.int64)
-        dx, dy, dz = x[c] - x[j], y[c] - y[j], z[c] - z[j]
-        d2 = dx * dx + dy * dy + dz * dz
-        assert d2.dtype == np.float32
-        out.append(lst[np.lexsort((lst["idx"], d2))])
-    return out
-
-
-def csr(lists):
-    from rustsasa_amd import NEIGHBOR_DTYPE
-    offs = np.zeros(len(lists) + 1, np.uint64)
-    offs[1:] = np.cumsum([len(lst) for lst in lists], dtype=np.uint64)
-    ent = np.concatenate([lst.astype(NEIGHBOR_DTYPE) for lst in lists]) if lists else np.zeros(0, NEIGHBOR_DTYPE)
-    return offs, ent
-
-
-def oracle_csr(x, y, z, r, ids, probe=PROBE, max_radius=None, **kw):
-    if max_radius is None:
-        max_radius = fold_max(r)
-    lists = po.neighbor_lists(x, y, z, r, ids, probe_radius=probe, max_radius=max_radius, **kw)
-    return csr(sorted_lists(lists, x, y, z))
-
-
-def assert_same(got, want):
-    go, ge = got
-    wo, we = want
-    assert np.array_equal(go, wo)
-    assert ge.tobytes() == we.tobytes()
-
-
-def protor(name):
-    xyz, r, _, ids = bw.fixture_soa(name)
-    x, y, z = (np.ascontiguousarray(xyz[:, k]).astype(np.float32) for k in range(3))
-    return x, y, z, _f32(r), ids
 
 
 # ---- the reference's unit case (tests/units.rs:132-209) ------------------------------------------------------------
@@ -216,7 +162,8 @@ def test_infinite_coordinate_then_usable(ctx):
 # ---- long lists: the global-memory staging -------------------------------------------------------------------------
 
 def test_spill_path_cluster(ctx):
-    """2 500 atoms inside one probe sphere plus a protein: K > 2 000 exceeds the fill kernel's LDS staging."""
+    """2 500 atoms inside one probe sphere plus a protein: K > 2 000, far above the fill kernel's LDS staging of 512
+    keys (kNbStage, neighbors.hip): the cluster's lists are ranked in global scratch (k_neighbor_rank_spill)."""
     x, y, z, r, ids = protor("1jcd.pdb")
     rng = np.random.default_rng(5)
     n = 2500

@@ -721,3 +721,70 @@ def pack(structures):
     so[1:] = np.cumsum([s.n for s in structures])
     cat = lambda name: np.concatenate([getattr(s, name) for s in structures])  # noqa: E731
     return cat("x"), cat("y"), cat("z"), cat("r"), cat("ids"), so
+
+
+# ---- the max_search cutoff of the neighbour lists (not part of generate(): the SASA path always uses max_r) --------
+
+@dataclass
+class MsCutoff:
+    """Atom 1 at d^2 == max_search^2 from atom 0 exactly (in f32) for max_radius `m_in`, max_radius given below r_0 so
+    the max_search test binds.  `inside` / `outside`: max_radius values (the flip and one more f32 step each way) for
+    which the oracle does / does not list atom 1 for atom 0."""
+    st: Structure
+    probe: float
+    m_in: float
+    inside: tuple
+    outside: tuple
+
+
+def _in_list0(st: Structure, probe, max_radius) -> bool:
+    lists = po.neighbor_lists(*st.soa(), probe_radius=probe, max_radius=max_radius)
+    return 1 in lists[0]["idx"].tolist()
+
+
+@functools.lru_cache(maxsize=None)
+def ms_cutoffs(seed: int = 20261017, want: int = 24):
+    """Pairs at exactly d^2 == max_search^2, max_search = 2 max_radius + 2 probe, with max_radius below r_0 (so
+    sr_0 = r_0 + max_radius + 2 probe is larger and only max_search decides): one coordinate of atom 1 is walked in
+    f32 steps to where d^2 <= max_search^2 flips and kept if d^2 equals max_search^2 there; then max_radius is walked
+    in f32 steps to where the oracle's list of atom 0 changes, which must be at that max_radius.  Kept: the cases the
+    oracle confirms on both sides, at the flip and one f32 step beyond it."""
+    rng = np.random.default_rng(seed)
+    out = []
+    attempts = 0
+    while len(out) < want and attempts < 400 * want:
+        attempts += 1
+        probe = F(rng.choice([1.4, 0.7, 0.0]))
+        m = F(rng.uniform(0.8, 1.6))
+        ri = F(m + F(rng.uniform(0.3, 1.0)))
+        rj = F(rng.uniform(0.5, 2.5))
+        ms = m + m + F(2.0) * probe
+        ms2 = ms * ms
+        u = _unit(rng, "diag" if len(out) % 2 else "random")
+        ci = F(rng.uniform(-20, 20, 3))
+        cj = F(ci - u * float(ms))
+        a = int(np.argmax(np.abs(u)))
+
+        def d2_of(xa, cj=cj, a=a):
+            q = cj.copy()
+            q[a] = xa
+            d = ci - q
+            return d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
+        flip = _walk_flip(lambda xa: not d2_of(xa) <= ms2, cj[a]) if u[a] < 0 else \
+            _walk_flip(lambda xa: d2_of(xa) <= ms2, cj[a])
+        if flip is None:
+            continue
+        x_in = flip[0] if u[a] < 0 else flip[1]
+        if d2_of(x_in) != ms2:
+            continue
+        q = cj.copy()
+        q[a] = x_in
+        st = Structure.of([ci, q], [ri, rj])
+        mflip = _walk_flip(lambda mr: _in_list0(st, probe, mr), m)
+        if mflip is None or mflip[1] != m:
+            continue  # (the grid's reach, not max_search, decides this pair)
+        inside, outside = (m, ulps(m, 1)), (mflip[0], ulps(mflip[0], -1))
+        if all(_in_list0(st, probe, v) for v in inside) and not any(_in_list0(st, probe, v) for v in outside):
+            out.append(MsCutoff(st, float(probe), float(m), tuple(float(v) for v in inside),
+                                tuple(float(v) for v in outside)))
+    return out
