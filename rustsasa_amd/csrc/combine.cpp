@@ -81,7 +81,6 @@ struct Block {
     std::mutex mu;
     std::condition_variable cv;
     bool done = false;
-    std::atomic<bool> done_flag{false};  // (the same, for members that spin a little before they sleep)
     int rc = RSASA_OK;
     std::string error;
     uint32_t consumed = 0;
@@ -150,10 +149,7 @@ int run_block(Combiner::Lane &lane, Block &b, int device, std::string *error)
         N += b.sizes[i];
     }
     if (!lane.ctx) {
-        // (RSASA_COMBINE_OWN_QUEUES=2: a hardware queue of its own for the lane's stream, context.cpp new_stream - measured no
-        // better with three lanes and worse with more: 148 k / 218 k against 153 k / 227 k on the runtime's pooled queues)
-        static const int own = [] { const char *v = tuning_env("RSASA_COMBINE_OWN_QUEUES"); return v ? std::atoi(v) : 0; }();
-        int rc = context_create(device, own, &lane.ctx);
+        int rc = context_create(device, 0, &lane.ctx);
         if (rc) { *error = "call combining: no context for the batch's lane"; return rc; }
     }
     rsasa_context *lc = lane.ctx;
@@ -195,7 +191,7 @@ int combine_call(rsasa_context *ctx, const SmallSource &in, size_t n_atoms, floa
     rq.has_id = in.has_id();
     {
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-        if (ctx->timing || ctx->tuning.debug_stop || !ctx->small_path) return kNotCombined;
+        if (ctx->timing || !ctx->small_path) return kNotCombined;
         rq.simd_width = ctx->simd_width;
         rq.tuning = ctx->tuning;
     }
@@ -237,7 +233,6 @@ int combine_call(rsasa_context *ctx, const SmallSource &in, size_t n_atoms, floa
             b->atoms = b->windows = 0;
             b->writers = 0;
             b->done = false;
-            b->done_flag.store(false, std::memory_order_relaxed);
             b->rc = RSASA_OK;
             b->consumed = 0;
             leader = true;
@@ -294,7 +289,6 @@ int combine_call(rsasa_context *ctx, const SmallSource &in, size_t n_atoms, floa
             b->rc = rc;
             b->error = error;
             b->done = true;
-            b->done_flag.store(true, std::memory_order_release);
         }
         b->cv.notify_all();
         cb.batches.fetch_add(1, std::memory_order_relaxed);
@@ -307,11 +301,6 @@ int combine_call(rsasa_context *ctx, const SmallSource &in, size_t n_atoms, floa
         const bool last_writer = --b->writers == 0 && b->state == Block::kClosed;
         lk.unlock();
         if (last_writer) cb.cv_lane.notify_all();
-        static const int spin_us = [] { const char *v = tuning_env("RSASA_COMBINE_SPIN_US"); return v ? std::atoi(v) : 0; }();
-        if (spin_us > 0) {
-            const uint64_t until = now_ns() + (uint64_t)spin_us * 1000u;
-            while (!b->done_flag.load(std::memory_order_acquire) && now_ns() < until) __builtin_ia32_pause();
-        }
         std::unique_lock<std::mutex> bl(b->mu);
         b->cv.wait(bl, [&] { return b->done; });
         rc = b->rc;

@@ -165,7 +165,6 @@ int reserve(rsasa_context *ctx, DeviceBuffer &b, size_t bytes)
         if (ctx->side_stream) RS_HIP(ctx, hipStreamSynchronize(ctx->side_stream));
         if (ctx->copy_stream) RS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
         if (ctx->d2h_stream) RS_HIP(ctx, hipStreamSynchronize(ctx->d2h_stream));
-        if (ctx->grid_stream) RS_HIP(ctx, hipStreamSynchronize(ctx->grid_stream));
         for (const Pending &pd : ctx->pending)
             if (pd.active && pd.stream && pd.stream != ctx->stream && pd.stream != ctx->stream2) RS_HIP(ctx, hipStreamSynchronize(pd.stream));
         RS_HIP(ctx, hipFree(b.p));
@@ -457,17 +456,8 @@ int enqueue_batch(rsasa_context *ctx, const Pending &pd, rsasa_context::HostSlot
     // Launch stream: grids -> LDS binning -> occlusion of the LDS-binned structures -> (join) ->
     // occlusion of the tail -> sums.  Side stream (forked after the LDS binning): the tail's
     // batch-wide binning, which is bandwidth bound and runs next to the compute-bound occlusion kernel.
-    // (RSASA_GRID_CUS experiment: the grid build on the stream of the reserved CUs, the rest behind an event)
-    const bool masked = ctx->grid_stream && (pd.stream == ctx->stream || pd.stream == ctx->stream2) && !(ctx->overlap_tail && has_tail);
-    hipStream_t gst = masked ? ctx->grid_stream : st;
-    if (masked) {
-        // the grid stream starts behind everything this batch has queued on its launch stream so far: the upload of the
-        // segments above and, on the pipelined host path, the wait for the sub-batch's input copies
-        RS_HIP(ctx, hipEventRecord(ctx->ev_grid_in[pd.ws], st));
-        RS_HIP(ctx, hipStreamWaitEvent(gst, ctx->ev_grid_in[pd.ws], 0));
-    }
-    if (ctx->timing) RS_HIP(ctx, hipEventRecord(W.ev[0], gst));
-    launch_grid_prepare(v, gst);
+    if (ctx->timing) RS_HIP(ctx, hipEventRecord(W.ev[0], st));
+    launch_grid_prepare(v, st);
     // Two batches in flight: this one's grid build is enqueued beside the other one's occlusion kernel (it gets the CUs
     // when that kernel's workgroups retire: the kernel leaves a CU no room), its occlusion kernel behind it.
     rsasa_context::Workspace &other = ctx->ws[pd.ws ^ 1];
@@ -489,13 +479,9 @@ int enqueue_batch(rsasa_context *ctx, const Pending &pd, rsasa_context::HostSlot
         RS_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
         launch_occlusion(v, lat, ctx->tuning, kOccRest, st);
     } else {
-        launch_sort_lds(v, gst);
-        if (has_tail) launch_sort_tail(v, gst);
-        if (ctx->timing) RS_HIP(ctx, hipEventRecord(W.ev[1], gst));
-        if (masked) {
-            RS_HIP(ctx, hipEventRecord(ctx->ev_grid[pd.ws], gst));
-            RS_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_grid[pd.ws], 0));
-        }
+        launch_sort_lds(v, st);
+        if (has_tail) launch_sort_tail(v, st);
+        if (ctx->timing) RS_HIP(ctx, hipEventRecord(W.ev[1], st));
         // (the wait for the other batch's occlusion kernel, the timing event and this batch's "occlusion kernel has ended"
         // event sit around the launch that does the work: OcclusionChain)
         OcclusionChain oc;
@@ -663,9 +649,7 @@ int rsasa_device_count(int *out_count)
 
 int rsasa_context_create(int device, rsasa_context_t **out_ctx)
 {
-    int own = 0;
-    if (const char *v = tuning_env("RSASA_CTX_OWN_QUEUES")) own = std::atoi(v);  // (experiment: DESIGN.md 6)
-    return context_create(device, own, out_ctx);
+    return context_create(device, 0, out_ctx);
 }
 
 }  // extern "C"
@@ -687,42 +671,7 @@ int rsasa::context_create(int device, int own_queues, rsasa_context_t **out_ctx)
     ctx->node = device_node_cpus(device);
     DeviceGuard guard(device);
     hipError_t e = guard.err;
-    if (const char *v = tuning_env("RSASA_GRID_CUS")) {
-        int n_cu = 0;
-        if (e == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0 && n_cu <= 512) {
-            const int want = std::atoi(v);
-            int stride = 1;  // RSASA_GRID_CU_STRIDE: reserved CUs are mask bits 0, stride, 2 stride, ...
-            if (const char *sv = tuning_env("RSASA_GRID_CU_STRIDE")) stride = std::max(1, std::atoi(sv));
-            if (want > 0 && want * stride <= n_cu && want < n_cu) {
-                ctx->grid_cus = (uint32_t)want;
-                ctx->cu_mask_words = (uint32_t)(n_cu + 31) / 32;
-                for (int c = 0; c < n_cu; c++) ctx->cu_rest[c / 32] |= 1u << (c % 32);
-                for (int k = 0; k < want; k++) {
-                    const int c = k * stride;
-                    ctx->cu_reserved[c / 32] |= 1u << (c % 32);
-                    ctx->cu_rest[c / 32] &= ~(1u << (c % 32));
-                }
-            }
-        }
-    }
-    if (e == hipSuccess && ctx->grid_cus) {
-        e = hipExtStreamCreateWithCUMask(&ctx->stream, ctx->cu_mask_words, ctx->cu_rest);
-        if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&ctx->stream2, ctx->cu_mask_words, ctx->cu_rest);
-        if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&ctx->grid_stream, ctx->cu_mask_words, ctx->cu_reserved);
-        for (int w = 0; w < 2 && e == hipSuccess; w++) e = hipEventCreateWithFlags(&ctx->ev_grid[w], hipEventDisableTiming);
-        for (int w = 0; w < 2 && e == hipSuccess; w++) e = hipEventCreateWithFlags(&ctx->ev_grid_in[w], hipEventDisableTiming);
-    } else if (e == hipSuccess) {
-        e = new_stream(ctx, &ctx->stream, 2);
-        // Experiment (RSASA_GRID_PRIO=1): the grid builds on a stream of the highest priority, so that their workgroups -
-        // shaped to fit the slot an occlusion workgroup leaves - are dispatched ahead of the other batch's
-        if (e == hipSuccess && tuning_env("RSASA_GRID_PRIO")) {
-            int least = 0, greatest = 0;
-            e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-            if (e == hipSuccess) e = hipStreamCreateWithPriority(&ctx->grid_stream, hipStreamNonBlocking, greatest);
-            for (int w = 0; w < 2 && e == hipSuccess; w++) e = hipEventCreateWithFlags(&ctx->ev_grid[w], hipEventDisableTiming);
-            for (int w = 0; w < 2 && e == hipSuccess; w++) e = hipEventCreateWithFlags(&ctx->ev_grid_in[w], hipEventDisableTiming);
-        }
-    }
+    if (e == hipSuccess) e = new_stream(ctx, &ctx->stream, 2);
     for (int w = 0; w < rsasa_context::kInFlight; w++) {
         for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipEventCreate(&ctx->ws[w].ev[i]);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ws[w].ev_occ, hipEventDisableTiming);
@@ -743,9 +692,6 @@ int rsasa::context_create(int device, int own_queues, rsasa_context_t **out_ctx)
     }
     if (const char *v = tuning_env("RSASA_OCCLUSION_KERNEL")) ctx->tuning.kernel_version = std::atoi(v);
     if (const char *v = tuning_env("RSASA_ATOMS_PER_WAVE")) ctx->tuning.atoms_per_wave = (uint32_t)std::atoi(v);
-#ifdef RSASA_ABLATE  // timing-ablation builds only (make ablate): the shipped library has no wrong-results switch
-    if (const char *v = tuning_env("RSASA_DEBUG_STOP")) ctx->tuning.debug_stop = (uint32_t)std::atoi(v);
-#endif
     if (const char *v = tuning_env("RSASA_OVERLAP_TAIL")) ctx->overlap_tail = std::atoi(v) != 0;
     if (const char *v = tuning_env("RSASA_SMALL_PATH")) ctx->small_path = std::atoi(v) != 0;
     *out_ctx = ctx;
@@ -809,11 +755,6 @@ int rsasa_context_destroy(rsasa_context_t *ctx)
             release(*b);
     }
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    if (ctx->grid_stream) (void)hipStreamDestroy(ctx->grid_stream);
-    for (hipEvent_t ev : ctx->ev_grid)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : ctx->ev_grid_in)
-        if (ev) (void)hipEventDestroy(ev);
     for (int i = 0; i < rsasa_context::kSlots; i++)
         if (ctx->ev_copy[i]) (void)hipEventDestroy(ctx->ev_copy[i]);
     for (int i = 0; i < rsasa_context::kSlots; i++) {

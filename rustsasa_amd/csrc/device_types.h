@@ -217,7 +217,6 @@ struct OcclusionTuning {
                                   // tests (4 and 5 leave the atoms they cannot take to the general kernel),
                                   // 6 = 5 for batches of 32 768 atoms or more, 4 below
     uint32_t atoms_per_wave = 0;  // 0 = choose from the batch size
-    uint32_t debug_stop = 0;      // RSASA_DEBUG_STOP: skip later kernel stages (WRONG results; timing ablation only)
     uint32_t deferred_hint = 0xFFFFFFFFu;  // atoms the context's last completed batch left to the general kernel (unknown at
                                            // first): sizes the launch that works off the next batch's deferred list - a grid-stride
                                            // loop, so any size is correct; 1 024 workgroups that find an empty list cost 20 us
@@ -271,13 +270,7 @@ void launch_expand_frames(const float *xyz, const float *radius, const uint64_t 
 
 constexpr uint32_t kSegmentAtoms = 4096;  // atoms per bounds workgroup
 constexpr uint32_t kScanBlocks = 1024;    // workgroups of the cell scan
-#ifndef RSASA_WINDOW_CELLS
-#define RSASA_WINDOW_CELLS 36864
-#endif
-#ifndef RSASA_SORT_THREADS
-#define RSASA_SORT_THREADS 1024
-#endif
-constexpr uint32_t kWindowCells = RSASA_WINDOW_CELLS;  // cells one k_sort_window workgroup bins (16-bit counters, 72 KiB: two per CU)
+constexpr uint32_t kWindowCells = 36864;  // cells one k_sort_window workgroup bins (16-bit counters, 72 KiB: two per CU)
 // k_ids_distinct (BatchView::ids_check): a table of 8 192 slots in LDS for structures of up to 4 096 atoms (32 KB: several
 // workgroups per CU), one of 36 864 for up to 27 648 (144 KB, one workgroup per such structure)
 // (the large table's entries are 16 bits wide - an atom's number within its structure, below 65 536 -: twice the slots in the

@@ -320,13 +320,6 @@ struct rsasa_context {
     } ws[2];
     static constexpr int kInFlight = 2;
     hipStream_t stream2 = nullptr;                // launch stream of workspace 1 (created by the first overlapped enqueue)
-    // Experiment (RSASA_GRID_CUS=N): N compute units are set aside for the grid builds - a stream masked to
-    // them - and the two launch streams are masked to the others, so batch k + 1's grid build runs BESIDE batch k's
-    // occlusion kernel instead of waiting for its workgroups to retire.
-    uint32_t grid_cus = 0, cu_mask_words = 0;
-    uint32_t cu_reserved[16] = {}, cu_rest[16] = {};
-    hipStream_t grid_stream = nullptr;
-    hipEvent_t ev_grid[2] = {nullptr, nullptr}, ev_grid_in[2] = {nullptr, nullptr};
     DeviceBuffer &segments = ws[0].segments, &acc = ws[0].acc, &grids = ws[0].grids, &grid_sums = ws[0].grid_sums,
                  &sid_sorted = ws[0].sid_sorted, &deferred_list = ws[0].deferred_list, &cell_of = ws[0].cell_of,
                  &rank_of = ws[0].rank_of, &cells = ws[0].cells, &windows = ws[0].windows, &scan_sums = ws[0].scan_sums,

@@ -258,7 +258,7 @@ int run_small_host_batch(rsasa_context *ctx, const SmallSource &in, const uint32
                          float *out_res)
 {
     if (S == 0 || S > kSmallStructures || so[0] != 0 || n_points == 0 || n_points > (1u << 24) ||
-        !(probe >= 0.0f) || !std::isfinite(probe) || ctx->timing || ctx->tuning.debug_stop)
+        !(probe >= 0.0f) || !std::isfinite(probe) || ctx->timing)
         return kNotSmall;
     const size_t N = so[S];
     if (N == 0 || N > kSmallAtoms) return kNotSmall;

@@ -393,22 +393,11 @@ __global__ __launch_bounds__(256) void k_grid_bases(BatchView b)
 // per-structure call, context.cpp run_small_host_batch).  They arrive as kernel arguments - no upload
 // precedes the launch, the inputs are read from pinned host memory - and the first workgroup stores
 // them where the later kernels look for them.
-constexpr uint32_t sort_window_threads(bool single) { return single ? 1024u : (uint32_t)RSASA_SORT_THREADS; }
-#ifdef RSASA_SORT_PROF
-// throw-away build (tools/sort_prof.py): per-phase time of k_sort_window, 10 ns ticks summed over workgroups
-__device__ unsigned long long g_sort_prof[16];
-#define SORT_STAMP(k) do { if (threadIdx.x == 0) { __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); \
-    atomicAdd(&g_sort_prof[k], t_ - t_prev_); t_prev_ = t_; } } while (0)
-#else
-#define SORT_STAMP(k)
-#endif
+constexpr uint32_t kSortWindowThreads = 1024u;
 template <bool SINGLE>
-__global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SORT_THREADS == 1024 ? 8 : 7)) void k_sort_window(BatchView b, SingleJob single)
+__global__ __launch_bounds__(kSortWindowThreads, SINGLE ? 4 : 8) void k_sort_window(BatchView b, SingleJob single)
 {
-    constexpr uint32_t kThreads = sort_window_threads(SINGLE);
-#ifdef RSASA_SORT_PROF
-    unsigned long long t_prev_ = __builtin_amdgcn_s_memrealtime();
-#endif
+    constexpr uint32_t kThreads = kSortWindowThreads;
     constexpr int kSlots = 8;                              // atoms per thread with position and coordinates in registers
     constexpr uint32_t kStage = kWindowCells * 2u / 32u;   // 32-byte records the counter memory stages
     constexpr uint32_t kPer = ((kWindowCells / 2u + kThreads - 1u) / kThreads) | 1u;  // counter words a thread scans (odd: no bank conflicts)
@@ -488,7 +477,6 @@ __global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SO
     }
     const uint32_t a_rest = a0 + kThreads * kSlots;  // first atom without a slot
     __syncthreads();
-    SORT_STAMP(0);
     // ---- count (spatial_grid.rs:53-62) ----
 #pragma unroll
     for (int k = 0; k < kSlots; k++) {
@@ -514,7 +502,6 @@ __global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SO
     }
     if (c0 && lane_id() == 0 && below) atomicAdd(&s_below, below);
     __syncthreads();
-    SORT_STAMP(1);
     // ---- exclusive scan (spatial_grid.rs:65-68): every thread owns kPer consecutive words (odd stride: no
     // bank conflicts), fetched in one go, sums them, the partial sums are scanned across the workgroup, and the
     // words are rewritten as (start of the even cell | start of the odd one << 16), counted from the
@@ -564,7 +551,6 @@ __global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SO
     // the upper half of the last word already (an empty cell's start), else the word after
     if (SINGLE && last_window && tid == 0 && (n_cells & 1u) == 0u) s_cnt[n_words] = g.n_atoms;
     __syncthreads();
-    SORT_STAMP(2);
     // ---- cell starts: the words as they are, eight cells per store ----
     {
         uint4 *out = reinterpret_cast<uint4 *>(reinterpret_cast<uint16_t *>(b.cells) + g.cell_base + c0);
@@ -572,7 +558,6 @@ __global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SO
         for (uint32_t i = tid; i < (n16 + 7u) / 8u; i += kThreads) out[i] = stage[i];
     }
     __syncthreads();  // the starts turn into the cells' cursors
-    SORT_STAMP(3);
     // ---- positions (spatial_grid.rs:70-93): an atom takes the next free position of its cell.
     // The order inside a cell is the order of arrival - the results do not depend on it.
 #pragma unroll
@@ -604,7 +589,6 @@ __global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SO
         }
     }
     __syncthreads();  // the cursors are dead: their memory stages the records, by position
-    SORT_STAMP(4);
     const uint32_t out0 = g.sorted_base + placed;  // this window's atoms are [out0, out0 + total)
     const uint32_t n_staged = min(total, kStage);
     // 32 bytes per atom: (x, y, z, radius) and (input index, id fold, id)
@@ -678,7 +662,6 @@ __global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SO
         }
     }
     __syncthreads();
-    SORT_STAMP(5);
     for (uint32_t j = tid; j < n_staged; j += kThreads) {
         const uint4 q = stage[2u * j + 1u];
         b.sorted_xyzr[out0 + j] = __builtin_bit_cast(float4, stage[2u * j]);
@@ -689,21 +672,7 @@ __global__ __launch_bounds__(sort_window_threads(SINGLE), SINGLE ? 4 : (RSASA_SO
         }
     }
     for (uint32_t j = tid; j < total; j += kThreads) b.sid_sorted[out0 + j] = s;
-#ifdef RSASA_SORT_PROF
-    __syncthreads();
-    SORT_STAMP(6);
-    if (threadIdx.x == 0) { atomicAdd(&g_sort_prof[8], 1ull); atomicAdd(&g_sort_prof[9], (unsigned long long)n_cells);
-                            atomicAdd(&g_sort_prof[10], (unsigned long long)total); atomicAdd(&g_sort_prof[11], (unsigned long long)g.n_atoms); }
-#endif
 }
-#ifdef RSASA_SORT_PROF
-extern "C" __attribute__((visibility("default"))) int rsasa_debug_sort_prof(unsigned long long *out)
-{
-    unsigned long long zero[16] = {};
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sort_prof), sizeof(zero)) != hipSuccess) return 1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_sort_prof), zero, sizeof(zero)) != hipSuccess;
-}
-#endif
 
 // ---- batch-wide path for the structures of the tail (cells do not fit the LDS) ----
 
@@ -868,14 +837,14 @@ void launch_grid_prepare(const BatchView &b, hipStream_t stream)
 // the surplus exits.
 void launch_sort_lds(const BatchView &b, hipStream_t stream)
 {
-    if (b.window_capacity) hipLaunchKernelGGL(k_sort_window<false>, dim3(b.window_capacity), dim3(sort_window_threads(false)), 0, stream, b, SingleJob{});
+    if (b.window_capacity) hipLaunchKernelGGL(k_sort_window<false>, dim3(b.window_capacity), dim3(kSortWindowThreads), 0, stream, b, SingleJob{});
 }
 
 // One structure, grid and status from the host (see k_sort_window<true>): one workgroup per window.
 void launch_sort_single(const BatchView &b, const SingleJob &job, hipStream_t stream)
 {
     const uint32_t n_win = grid_windows(job.grid.n_cells);
-    if (n_win) hipLaunchKernelGGL(k_sort_window<true>, dim3(n_win), dim3(sort_window_threads(true)), 0, stream, b, job);
+    if (n_win) hipLaunchKernelGGL(k_sort_window<true>, dim3(n_win), dim3(kSortWindowThreads), 0, stream, b, job);
 }
 
 // Batch-wide binning of the other structures (the tail).  Independent of launch_sort_lds: the

@@ -50,7 +50,6 @@ struct OccArgs {
     Lattice lat;
     uint32_t n_blocks;        // launched workgroups (for the XCD swizzle)
     uint32_t atoms_per_wave;  // consecutive cell-sorted atoms handled by one wave
-    uint32_t debug_stop;      // timing ablation (v3 only)
 };
 
 #include "occlusion_v0.inc"
@@ -204,14 +203,14 @@ void launch_occlusion(const BatchView &b, const Lattice &lat, const OcclusionTun
         ~ChainGuard() { begin(); if (!ended) chain_end(chain, stream); }
     } guard{chain, stream};
     if (!b.n_atoms) return;
-    OccArgs a{b, lat, 0, 1, tune.debug_stop};
+    OccArgs a{b, lat, 0, 1};
     const uint32_t n_chunks = (lat.n_points + kWave - 1) / kWave;
     // the straight-line kernels: few remainder points; up to 128 points (k_occlusion_fast), or up to
     // kMxMaxPoints with the matrix-core kernel
     // (6 = default: the matrix-core kernel once the batch has enough atoms to fill the GPU with its
     // 64-atom waves; smaller batches - single structures - finish sooner on the per-atom kernels)
     const bool mx = occlusion_uses_mx(tune, lat, b.n_atoms);
-    const bool fast = tune.kernel_version >= 4 && tune.debug_stop == 0 && (n_chunks <= 2 || mx) &&
+    const bool fast = tune.kernel_version >= 4 && (n_chunks <= 2 || mx) &&
                       lat.n_points - lat.n_fused <= kFastMaxRem;
     if (!fast && part == kOccHead) return;  // only the fast kernel takes a partial range
     if (!(fast && mx)) guard.begin();  // (launch_mx places the chain's events around its working launch)
@@ -297,50 +296,34 @@ void launch_occlusion(const BatchView &b, const Lattice &lat, const OcclusionTun
         // busy twice over (16 at least; all 1 024 while nothing is known)
         const uint32_t want = tune.deferred_hint == 0xFFFFFFFFu ? 1024u : min(1024u, max(16u, cdiv(tune.deferred_hint, 2u)));
         const uint32_t n_blocks = min(cdiv(b.n_atoms, 4), want);
-        if (b.id) hipLaunchKernelGGL((k_occlusion_v3<2, true, false>), dim3(n_blocks), dim3(256), 0, stream, a3);
-        else hipLaunchKernelGGL((k_occlusion_v3<2, false, false>), dim3(n_blocks), dim3(256), 0, stream, a3);
+        if (b.id) hipLaunchKernelGGL((k_occlusion_v3<2, true>), dim3(n_blocks), dim3(256), 0, stream, a3);
+        else hipLaunchKernelGGL((k_occlusion_v3<2, false>), dim3(n_blocks), dim3(256), 0, stream, a3);
         return;
     }
-#ifdef RSASA_ABLATE  // timing ablation build (make ablate, tools/ablate.sh): results are wrong; not in the shipped library
-    if (tune.debug_stop != 0) {
-        if (b.id) hipLaunchKernelGGL((k_occlusion_v3<2, true, true>), dim3(a.n_blocks), dim3(256), 0, stream, a3);
-        else hipLaunchKernelGGL((k_occlusion_v3<2, false, true>), dim3(a.n_blocks), dim3(256), 0, stream, a3);
-    } else
-#endif
     if (b.id) {
-        hipLaunchKernelGGL((k_occlusion_v3<2, true, false>), dim3(a.n_blocks), dim3(256), 0, stream, a3);
+        hipLaunchKernelGGL((k_occlusion_v3<2, true>), dim3(a.n_blocks), dim3(256), 0, stream, a3);
     } else {
-        hipLaunchKernelGGL((k_occlusion_v3<2, false, false>), dim3(a.n_blocks), dim3(256), 0, stream, a3);
+        hipLaunchKernelGGL((k_occlusion_v3<2, false>), dim3(a.n_blocks), dim3(256), 0, stream, a3);
     }
 }
 
 bool occlusion_uses_mx(const OcclusionTuning &tune, const Lattice &lat, uint32_t n_atoms)
 {
-    return tune.kernel_version >= 5 && tune.debug_stop == 0 && lat.n_points <= kMxMaxPoints &&
+    return tune.kernel_version >= 5 && lat.n_points <= kMxMaxPoints &&
            lat.n_points - lat.n_fused <= kFastMaxRem && (tune.kernel_version == 5 || n_atoms >= kMxMinAtoms);
 }
 
 void launch_occlusion_deferred(const BatchView &b, const Lattice &lat, hipStream_t stream)
 {
     if (!b.n_atoms) return;
-    OccArgs a{b, lat, 0, 1, 0};
+    OccArgs a{b, lat, 0, 1};
     OccArgs3 a3 = make_args3(a);
     a3.work_list = b.deferred_list;
     a3.work_count = &b.status->deferred;
     a3.atoms_per_wave = 1;
     const uint32_t n_blocks = min(cdiv(b.n_atoms, 4), 1024u);
-    if (b.id) hipLaunchKernelGGL((k_occlusion_v3<2, true, false>), dim3(n_blocks), dim3(256), 0, stream, a3);
-    else hipLaunchKernelGGL((k_occlusion_v3<2, false, false>), dim3(n_blocks), dim3(256), 0, stream, a3);
+    if (b.id) hipLaunchKernelGGL((k_occlusion_v3<2, true>), dim3(n_blocks), dim3(256), 0, stream, a3);
+    else hipLaunchKernelGGL((k_occlusion_v3<2, false>), dim3(n_blocks), dim3(256), 0, stream, a3);
 }
 
 }  // namespace rsasa
-
-#ifdef MX_STAGE_PROF
-// diagnostic build only (tools/mx_stage_prof.py): the stage stamps of k_occlusion_mx summed over every wave since the last call
-extern "C" __attribute__((visibility("default"))) int rsasa_debug_mx_prof(unsigned long long *out)
-{
-    unsigned long long zero[16] = {};
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(rsasa::g_mx_prof), sizeof(zero)) != hipSuccess) return 1;
-    return hipMemcpyToSymbol(HIP_SYMBOL(rsasa::g_mx_prof), zero, sizeof(zero)) != hipSuccess;
-}
-#endif

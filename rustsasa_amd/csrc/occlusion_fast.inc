@@ -22,10 +22,7 @@ constexpr int kFastCap = 144;              // candidate records per wave (LDS: 8
 constexpr uint32_t kFastMaxSwept = 256;    // atoms in the culled runs (one run-start mask window)
 constexpr uint32_t kFastMaxRem = 4;        // remainder points held in SGPRs
 constexpr int kFastAtomsPerWave = 10;      // 250 (atom, run) pairs fill four prologue passes
-#ifndef FAST_TILE_STEPS
-#define FAST_TILE_STEPS 2
-#endif
-constexpr int kTileSteps = FAST_TILE_STEPS;   // phase-B tile steps (LDS reads in flight) per trip: 2 or 4 (no difference measured)
+constexpr int kTileSteps = 2;                 // phase-B tile steps (LDS reads in flight) per trip: 2 or 4 (no difference measured)
 constexpr int kCandPad = 8 * kTileSteps;      // -inf records behind the candidate list (tile over-read)
 
 

@@ -155,33 +155,14 @@ __device__ __forceinline__ uint32_t mbcnt64_add(unsigned long long m, uint32_t a
 // the union's records in a group's prologue, the result stores at the end - issues ahead of the waves that are in their
 // atom loops, which have instructions to spare: - 0.8 % (measured one by one: group prologue - 0.6 %, start and end
 // - 0.2 %; raising the point tests or the sweep instead: + 0.5 % / + 0.7 %).
-#define MX_PRIO_GROUP 2
-#define MX_PRIO_START 3
-#define MX_PRIO_END 3
+constexpr int kMxPrioGroup = 2;
+constexpr int kMxPrioStart = 3;
+constexpr int kMxPrioEnd = 3;
 // Phase A's two point operands (launches with at most 128 points) do not depend on the atom: a lane keeps its 2 x 8 bytes
 // in registers for the wave's lifetime instead of fetching them from the LDS table for every atom (two reads and one LDS
 // round trip in front of the second matrix instruction): -0.9 % (only the first: no gain; both fetched per atom, but beside the
 // candidates: +1.5 %).
 constexpr bool mx_persistent(bool multi) { return multi; }  // (persistent waves at 100 points too: +2.7 %, tools/experiments)
-
-// Diagnostic builds of round 5 (never the shipped library; both leave the results wrong or untouched as stated):
-//   -DMX_STAGE_PROF   s_memtime stamps at the stage boundaries of the atom loop and around a group's prologue; lane 0 adds
-//                     the deltas to per-wave LDS words, the wave adds those to g_mx_prof at its end (a buffer of its own:
-//                     no output is computed from a stamp).  tools/mx_stage_prof.py prints cycles per atom and stage.
-//   -DMX_ABLATE=n     the atom loop stops early: 1 no phase B, 2 no phase A / B, 3 no prep either, 4 no sweep either,
-//                     5 no atom loop at all (group work only).  RESULTS ARE WRONG BY DESIGN: the kernel's time against
-//                     the full build's is what a stage costs the LAUNCH (throughput), where the stamps give what it
-//                     costs a WAVE (latency).  tools/mx_ablate.sh.
-#ifdef MX_STAGE_PROF
-__device__ unsigned long long g_mx_prof[16];
-#define MX_STAMP(k) do { const uint32_t t_ = (uint32_t)__builtin_amdgcn_s_memtime(); \
-                         if (lane == 0) atomicAdd(&s_prof[w][k], t_ - t_prev_); t_prev_ = t_; } while (0)
-#else
-#define MX_STAMP(k)
-#endif
-#ifndef MX_ABLATE
-#define MX_ABLATE 0
-#endif
 
 template <int NT, bool HAS_ID, bool HAS_REM, bool MULTI, int NW>
 __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 waves per workgroup: LDS keeps 6 waves per SIMD or fewer */ __attribute__((amdgpu_num_sgpr(MX_MAX_SGPR))) void k_occlusion_mx(OccArgs3 a)
@@ -257,10 +238,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
     constexpr uint32_t kWaveAtoms = MULTI ? kMxAtomsMulti : kMxAtoms;  // (the launch keeps atoms_per_wave within it)
     __shared__ float4 s_atom[NW][kWaveAtoms];   // the wave's atoms (x, y, z, r): broadcast reads per atom instead of
     __shared__ uint2 s_aux[NW][kWaveAtoms];     // readlanes; (id fold, 1 / (2 (r + probe)) correctly rounded)
-#ifdef MX_STAGE_PROF
-    __shared__ uint32_t s_prof[NW][16];
-    if ((threadIdx.x & 63u) < 16u) s_prof[threadIdx.x >> 6][threadIdx.x & 63u] = 0u;
-#endif
 
     const float4 *__restrict__ sorted_xyzr = a.sorted_xyzr;
     const uint32_t *__restrict__ sorted_id32 = a.sorted_id32;
@@ -305,9 +282,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         if (i < NP) s_pt16[i] = __builtin_bit_cast(uint2, h);
     }
     __syncthreads();
-#ifdef MX_CLOCK  // diagnostic build (tools/mx_clock.sh): the shader clock a wave sees over its lifetime; never the shipped library
-    const unsigned long long clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
 
     // The launch covers the cell-sorted positions [lo, hi) (see k_occlusion_fast); each XCD gets a
     // contiguous piece.
@@ -333,11 +307,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
     // tiles with the band's minimum for every atom that had one alive - 100 points with 4 remainder points ran 5 % SLOWER
     // than 104 points with none: 3.42 against 3.25 ms; 1 M atoms x 964 points 9 % slower than x 960.)
     constexpr bool kRemApart = HAS_REM;  // (more than 128 points as well: the filter's trips pick the remainder points out, below)
-#if defined(MX_STAGE_PROF) || MX_ABLATE || defined(MX_STAT)
-    constexpr bool kPhaseBAtOnce = false;  // (the diagnostic builds stamp / cut between the survivors' stores and the exact tests)
-#else
     constexpr bool kPhaseBAtOnce = !MULTI;
-#endif
     const unsigned long long okf1 = kRemApart ? ok1 & ~rem1 : ok1, okf2 = kRemApart ? ok2 & ~rem2 : ok2;  // the fused-rule points
     // row of the 5x5 block this lane looks up in a group's prologue (lanes 0..24), the group's own row (12) in lane 0:
     // its atoms - the group's among them - then come first in the union
@@ -375,10 +345,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
     // loops they were spilled to vector-register lanes there (42 v_readlane / 15 v_writelane against 15 / 0) and the
     // launches with 100 points lost 3.5 %.
     constexpr bool kPersist = mx_persistent(MULTI);
-#ifdef MX_DEBUG_XCC  // diagnostic build: which XCD a workgroup runs on (HW_REG_XCC_ID, bits 3:0)
-    if (lane == 0 && w == 0 && (blockIdx.x < 40u || (blockIdx.x % 397u) == 0u))
-        printf("MXXCC block %u xcc %u\n", blockIdx.x, (uint32_t)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)));
-#endif
     {
         const uint32_t n_wblocks = (hi - lo + apw - 1u) / apw;
         if (kPersist) {
@@ -404,9 +370,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         }
         wave_lds_fence();
     }
-#ifdef MX_STAGE_PROF
-    uint32_t t_prev_ = (uint32_t)__builtin_amdgcn_s_memtime();
-#endif
     for (;; ) {
     uint32_t w_begin, n_mine, hi_b;
     {
@@ -419,9 +382,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         w_begin = (uint32_t)__builtin_amdgcn_readfirstlane((int)q0.x) + in_piece * apw_b;
         n_mine = min(apw_b, hi_b - w_begin);
     }
-#if MX_PRIO_START
-    __builtin_amdgcn_s_setprio(MX_PRIO_START);
-#endif
+    __builtin_amdgcn_s_setprio(kMxPrioStart);
 
     // ---- the wave's atoms, lane = atom ----
     const uint32_t pa = min(w_begin + lane, hi_b - 1u);
@@ -474,9 +435,7 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         const uint32_t p_bx = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bx, 0x138, 0xf, 0xf, false);
         starts = ballot64(lane == 0u || p_sid != my_sid || p_cy != cy || p_cz != cz || p_bx != bx);
     }
-#if MX_PRIO_START
     __builtin_amdgcn_s_setprio(0);
-#endif
     wave_lds_fence();  // the atoms' LDS records are read from here on
     const unsigned long long mine_mask = n_mine >= 64u ? ~0ull : ((1ull << n_mine) - 1ull);
 
@@ -493,7 +452,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
     bool rel16 = false;  // the structure's cell entries: 16-bit, relative to rel_base (else 32-bit absolute)
     float max_r = 0.f;
     bool not_mine = false;  // the current structure belongs to the other instantiation of the pair (its ids matter / do not)
-    MX_STAMP(0);  // the wave's start: point tables, its atoms, group starts
     while (g0 < n_mine) {
         // ---- the group [g0, g1): until the next group start, narrowed if its union is too large ----
         uint32_t g1;
@@ -524,19 +482,8 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         const uint32_t gxyz = readlane_u(cxyz, g0);
         const uint32_t gcy = (gxyz >> 10) & 1023u, gcz = gxyz >> 20;
         const uint32_t cx_first = gxyz & 1023u;
-#if MX_PRIO_GROUP
-        __builtin_amdgcn_s_setprio(MX_PRIO_GROUP);
-#endif
+        __builtin_amdgcn_s_setprio(kMxPrioGroup);
         uint32_t U, run_start, excl, n_chunk;
-#ifdef MX_PAD_GROUP  // diagnostic build (DESIGN 6a, tools/mx_pad.sh): the prologue's run look-ups, scan and union gathers are done
-        uint32_t pad_reps = 1u + MX_PAD_GROUP;  // MX_PAD_GROUP more times per group (same values into the same registers): what the kernel's time
-        asm volatile("" : "+s"(pad_reps));      // gains is what a prologue costs the LAUNCH beside the other stages
-        float4 un[NS];
-        uint32_t uid[NS];
-        uint32_t self0 = 0;
-        for (uint32_t pad_rep = 0; pad_rep < pad_reps; pad_rep++) {
-        asm volatile("" : "+s"(g1), "+v"(cxyz));
-#endif
         for (;;) {
             const uint32_t cx_last = readlane_u(cxyz, g1 - 1u) & 1023u;
             const uint32_t x_lo = cx_first >= 2u ? cx_first - 2u : 0u;
@@ -574,15 +521,11 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         }
         n_chunk = (min(U, kUnion) + 63u) >> 6;
         // the group's own row is the first run (lane 0): position of atom g0 inside the union
-#ifdef MX_PAD_GROUP
-        self0 = w_begin + g0 - readlane_u(run_start, 0);
-#else
         const uint32_t self0 = w_begin + g0 - readlane_u(run_start, 0);
 
         // ---- the union in registers: lane = slot of chunk c ----
         float4 un[NS];
         uint32_t uid[NS];
-#endif
         {
             const uint32_t mword = lane < 2u * (uint32_t)NS ? s_mask[w][lane] : 0u;
             uint32_t base_rank = 0;
@@ -608,21 +551,10 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
                 }
             }
         }
-#ifdef MX_PAD_GROUP
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (a repetition's gathers have arrived before the next one starts: as in a real prologue, whose atom loop reads them)
-        }
-#endif
-#if MX_PRIO_GROUP
         __builtin_amdgcn_s_setprio(0);
-#endif
         // (the claim has come back by now - it is older than the gathers above -, and no register has to carry it
         // through the atom loops)
         if (kPersist && g0 == 0u && lane == 0u) s_blk[w][3] = s_blk[w][2] + next_claim;
-#ifdef MX_STAGE_PROF
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the union's records have arrived: their latency belongs to the prologue)
-        MX_STAMP(1);  // group prologue: run lookups, scan, union gathers
-        if (lane == 0) { atomicAdd(&s_prof[w][8], 1u); atomicAdd(&s_prof[w][9], g1 - g0); atomicAdd(&s_prof[w][10], n_chunk); }
-#endif
         // The general kernel takes the whole group when a single cell has more than 256 atoms around it, when a
         // radius is out of range (ok_atoms), or when the group's atoms do not all sit in the union's first
         // chunk (the sweep excludes an atom from its own list there and nowhere else).
@@ -642,25 +574,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         // lane l is the atom's own slot of chunk 0 when l == self0 + (at - g0): l - self0 + g0 == at, the left side made once per group
         const uint32_t self_v = lane - vgpr_u(self0) + vgpr_u(g0);
         for (uint32_t at = g0; at < g1; at++, at_v = vadd_u(at_v, 1u)) {
-#ifdef MX_PAD_VALU  // diagnostic builds (DESIGN 6a): what one more vector / scalar instruction per atom costs
-#pragma unroll
-            for (int pad = 0; pad < MX_PAD_VALU; pad += 2) asm volatile("v_mov_b32 %0, %0\n v_mov_b32 %0, %0" : "+v"(at_v));
-#endif
-#ifdef MX_PAD_VALU8  // ... the same instruction in its 8-byte encoding: what the BYTES of an instruction cost (instruction fetch)
-#pragma unroll
-            for (int pad = 0; pad < MX_PAD_VALU8; pad += 2) asm volatile("v_mov_b32_e64 %0, %0\n v_mov_b32_e64 %0, %0" : "+v"(at_v));
-#endif
-#ifdef MX_PAD_NOP  // ... and instructions that use no unit at all (s_nop 0: fetched, decoded, issued to nothing)
-#pragma unroll
-            for (int pad = 0; pad < MX_PAD_NOP; pad++) asm volatile("s_nop 0");
-#endif
-#ifdef MX_PAD_SALU
-#pragma unroll
-            for (int pad = 0; pad < MX_PAD_SALU; pad++) asm volatile("s_mov_b32 %0, %0" : "+s"(g0));
-#endif
-#ifdef MX_SLEEP  // diagnostic build (DESIGN 6a): pure latency per atom - s_sleep n parks the wave for about 64 n cycles and uses no unit
-            __builtin_amdgcn_s_sleep(MX_SLEEP);
-#endif
             const float4 me = s_atom[w][at_v];  // (one address in all lanes: broadcast reads)
             const uint2 aux = s_aux[w][at_v];
             const float mx = me.x, my = me.y, mz = me.z, mr = me.w;
@@ -692,11 +605,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
                 }
                 K += (uint32_t)__popcll(m);
             };
-            if (MX_ABLATE >= 4) {  // (diagnostic: no sweep; the union stays live through one of its registers)
-                if (lane == at) my_result = (mid ^ __float_as_uint(un[0].x + mx)) & 0x7FFFu;
-                wave_lds_fence();
-                continue;
-            }
             sweep_chunk(un[0], uid[0], 0);
             if (NCH ? NCH > 1u : n_chunk > 1u) sweep_chunk(un[1], uid[1], 1);
             if (NCH ? NCH > 2u : n_chunk > 2u) sweep_chunk(un[2], uid[2], 2);
@@ -713,22 +621,12 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
                     a.work_list_out[atomicAdd(a.work_count_out, 1u)] = w_begin + at;
                 }
                 wave_lds_fence();
-                MX_STAMP(7);
                 continue;
             }
             wave_lds_fence();
-            MX_STAMP(2);  // atom header + sweep
-            if (MX_ABLATE == 3) {  // (diagnostic: nothing behind the sweep)
-                if (lane == at) my_result = K & 0x7FFFu;
-                wave_lds_fence();
-                continue;
-            }
 
             // -- prep (lane = candidate), in place: record (x, y, z, r) -> operand record (vz, vy, vx, limit).
             // Lanes beyond the list read whatever the buffer holds (finite numbers) and get limit -inf.
-#ifdef MX_STAT
-            uint32_t stat_S = 0;
-#endif
             auto prep_pass = [&](const uint32_t k0, const bool first) {
                 const uint32_t k = k0 + lane;
                 const unsigned long long live = ballot64(k < K);
@@ -752,9 +650,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
                     // near candidates (strong occluders) first; a permutation inside this pass's slots
                     // (padding lanes come after every near lane: they keep slot k)
                     const unsigned long long mN = ballot64(d2 < near2) & live;
-#ifdef MX_STAT
-                    if (MX_STAT == 2) stat_S = (uint32_t)__popcll(mN);  // near candidates (of the first 64)
-#endif
                     const uint32_t before = mbcnt64_add(mN, 0u);
                     slot = vsel(mN, (uint32_t)__popcll(mN) + k - before, before);
                 }
@@ -784,12 +679,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
             prep_pass(0u, true);
             if (K > 64u) prep_pass(64u, false);
             wave_lds_fence();
-            MX_STAMP(3);  // prep
-            if (MX_ABLATE == 2) {  // (diagnostic: nothing behind prep; one operand record read back)
-                if (lane == at) my_result = (K + (wl.c16[lane & 15u].x & 1u)) & 0x7FFFu;
-                wave_lds_fence();
-                continue;
-            }
 
             // -- point tests.
             // PHASE A, a filter on the f16 matrix instruction: tile 0 against all points (the remainder points
@@ -950,9 +839,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
                         n_live += (uint32_t)__popcll(live);
                     }
                     wave_lds_fence();
-#ifdef MX_STAT
-                    if (MX_STAT == 4) stat_S = n_live;
-#endif
                     // FILTER on the live tiles, eight per trip (two instructions of four tiles)
                     const uint32_t rowt = ((lrow & 1u) << 1) | (lrow >> 1);  // the tile of the four whose points the fold leaves in this lane's row
                     for (uint32_t t0 = 0; t0 < n_live; t0 += 8u) {
@@ -1011,12 +897,6 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
                         if (kPhaseBAtOnce) phase_b();  // (one test of S for the stores and the exact tests)
                     }
                 }
-#ifdef MX_STAT
-                if (MX_STAT != 4 && MX_STAT != 2) stat_S = n_sv;
-                if (MX_STAT == 5) stat_S = (uint32_t)__popcll(rem_left);  // remainder points the filter left alive
-#endif
-                MX_STAMP(4);  // phase A (filter, survivors' indices stored)
-                if (MX_ABLATE == 1) { exposed += n_sv; n_sv = 0u; }  // (diagnostic: no exact tests)
                 if (!kPhaseBAtOnce && n_sv != 0u) phase_b();
                 if (kRemApart && MULTI && rem_alive4 != 0u) phase_b_rem(rem_alive4);
                 if (kRemApart && !MULTI && rem_left != 0ull) {
@@ -1025,32 +905,20 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
                     const uint32_t pf = n_fused & 63u, t = pf >> 4;
                     phase_b_rem((uint32_t)(rem_left >> (16u * (((t & 1u) << 1) | (t >> 1)) + (pf & 15u))));
                 }
-                MX_STAMP(5);  // phase B
             }
-#ifdef MX_STAT  // statistics build (tools/mx_stats.py): a per-atom quantity instead of the candidate count
-            if (lane == at) my_result = exposed | (((MX_STAT == 1 || MX_STAT == 2 || MX_STAT == 4 || MX_STAT == 5 ? stat_S : n_tiles)) << 16);  // 1: survivors of phase A, 2: near candidates, 4: live tiles after the patch test, 5: remainder points alive after the filter, else candidate tiles
-            else
-#endif
             if (lane == at) my_result = exposed | (K << 16);  // lib.rs:156-159,215-217 (K: only read when counts are asked for)
             wave_lds_fence();
-            MX_STAMP(6);  // result word, loop
         }
         };
-#if MX_ABLATE >= 5  // (diagnostic: group work only)
-        if (lane >= g0 && lane < g1) my_result = (__float_as_uint(un[0].x) ^ uid[0]) & 0x7FFFu;
-#else
         if (n_chunk == 3u) atoms_of_group(std::integral_constant<uint32_t, 3u>{});
         else if (NS == 5 && n_chunk == 5u) atoms_of_group(std::integral_constant<uint32_t, 5u>{});
         else if (n_chunk == 4u) atoms_of_group(std::integral_constant<uint32_t, 4u>{});
         else if (n_chunk == 2u) atoms_of_group(std::integral_constant<uint32_t, 2u>{});
         else atoms_of_group(std::integral_constant<uint32_t, 1u>{});
-#endif
         g0 = g1;
     }
 
-#if MX_PRIO_END
-    __builtin_amdgcn_s_setprio(MX_PRIO_END);
-#endif
+    __builtin_amdgcn_s_setprio(kMxPrioEnd);
     // ---- results of the wave's atoms, one lane each ----
     if (lane < n_mine && my_result != kDeferred) {
         if (kPersist) asm volatile("" : "+s"(ka));
@@ -1064,25 +932,8 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         (kPersist ? ka->atom_sasa : a.atom_sasa)[orig] = surface_area * accessible * inv_n;  // lib.rs:222
         if (counts) counts[orig] = my_result >> 16;
     }
-#if MX_PRIO_END
     __builtin_amdgcn_s_setprio(0);
-#endif
     wave_lds_fence();  // (the next block's atoms overwrite s_atom)
-#ifdef MX_STAGE_PROF
-    MX_STAMP(11);  // results out
-    if (lane == 0) { atomicAdd(&s_prof[w][12], n_mine); atomicAdd(&s_prof[w][13], 1u); }
-#endif
     if (!kPersist) break;
     }  // next block
-#ifdef MX_STAGE_PROF
-    wave_lds_fence();
-    if (lane < 16u) atomicAdd(&g_mx_prof[lane], (unsigned long long)s_prof[w][lane]);
-#endif
-#ifdef MX_CLOCK
-    {
-        const unsigned long long clk_t1 = __builtin_amdgcn_s_memtime(), clk_r1 = __builtin_amdgcn_s_memrealtime();
-        if (lane == 0 && w == 0 && (blockIdx.x & 2047u) == 0u)
-            printf("MXCLK block %u cycles %llu ticks100MHz %llu\n", blockIdx.x, clk_t1 - clk_t0, clk_r1 - clk_r0);
-    }
-#endif
 }

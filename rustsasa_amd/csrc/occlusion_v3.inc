@@ -1,14 +1,14 @@
-// The production occlusion kernel (k_occlusion_v3); the stages are described at the top of
-// occlusion.hip.  It is bound by VALU + SALU issue (~1.15 ns per wave-instruction and SIMD,
-// tools/microbench_issue.hip), so the design choices below are about instruction count:
+// The general occlusion kernel (k_occlusion_v3): it decides the atoms the other kernels defer,
+// and every atom when they do not apply (more points or remainder points than they take, or
+// RSASA_OCCLUSION_KERNEL=3).  The stages are described at the top of occlusion.hip.  It is bound
+// by VALU + SALU issue (~1.15 ns per wave-instruction and SIMD, tools/microbench_issue.hip), so
+// the design choices below are about instruction count:
 //   * a dense prologue computes the culled runs of all the wave's atoms, 64 (atom, run) pairs
 //     per pass; the per-atom prefix sum uses DPP, not LDS permutes;
 //   * the sweep only tests distances and appends the accepted atom's INDEX (4-byte LDS store,
 //     exec-masked: LDS stores cost by active lane); the prep pass (lane = candidate) re-gathers
 //     the atom, applies the id rule, computes (v, limit) and writes the near-first list once;
 //   * survivors are compacted as point indices and re-read from the lattice (float4 records).
-// RSASA_DEBUG_STOP=n (tools/ablate.sh) skips the stages after point n to time them; results
-// are wrong in such runs.
 
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ uint32_t dpp_zero(uint32_t src)
@@ -34,10 +34,7 @@ constexpr int kSegShift = 4;
 constexpr int kMaxAtomsPerWave = 8;        // atoms one wave prepares in its prologue
 constexpr int kListCap = 192;              // queued candidate indices per wave
 constexpr int kListFlush = kListCap - 64;  // flush once more than this many are queued
-#ifndef RSASA_NEAR_SCALE2
-#define RSASA_NEAR_SCALE2 1.5625f
-#endif
-constexpr float kNearScale2 = RSASA_NEAR_SCALE2;  // near: d^2 < (1.25 (r_i + p))^2 -- heuristic split only
+constexpr float kNearScale2 = 1.5625f;  // near: d^2 < (1.25 (r_i + p))^2 -- heuristic split only
 
 // Only what the kernel reads: a small argument block keeps the SGPR file free of spills.
 struct OccArgs3 {
@@ -55,7 +52,6 @@ struct OccArgs3 {
     uint32_t *neighbor_counts;
     uint32_t n_atoms, n_points, n_fused, n_blocks, atoms_per_wave;
     float probe;
-    uint32_t debug_stop;  // 0 = full kernel; >0 = skip the stages after that point (timing ablation only)
     // deferred atoms: written by k_occlusion_fast, consumed by k_occlusion_v3 in list mode
     // (work_list != nullptr: the wave's atoms are work_list[i], i < *work_count, grid-stride)
     uint32_t *work_list_out, *work_count_out;
@@ -76,11 +72,11 @@ inline OccArgs3 make_args3(const OccArgs &a)
     return OccArgs3{a.b.sorted_xyzr, a.b.cells, a.b.sid_sorted, a.b.sorted_orig, a.b.grids, a.b.sorted_id, a.b.id, a.b.sorted_id32,
                     a.b.status, a.lat.x, a.lat.y, a.lat.z, a.lat.xyz4, a.lat.patches, a.b.atom_sasa,
                     a.b.neighbor_counts, a.b.n_atoms, a.lat.n_points, a.lat.n_fused, a.n_blocks,
-                    a.atoms_per_wave, a.b.probe, a.debug_stop, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, a.lat.mx_tab, a.b.ids_check,
+                    a.atoms_per_wave, a.b.probe, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr, a.lat.mx_tab, a.b.ids_check,
                     a.b.ids_check ? a.b.ids_seg : nullptr, a.b.ids_seg_words};
 }
 
-template <int NCH, bool HAS_ID, bool ABLATE>
+template <int NCH, bool HAS_ID>
 __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
 {
     if (batch_aborted(a.status)) return;
@@ -241,11 +237,7 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
 
         float accessible = 0.0f;
         uint32_t k_total = 0;
-        uint32_t stat = 0;  // ABLATE builds, debug_stop >= 10: a per-atom statistic instead of k_total
-        const uint32_t stat_sel = ABLATE ? a.debug_stop : 0u;
-        if (stat_sel == 10u) stat = n_seg_total;
         bool all_groups = false;
-        if (ABLATE && a.debug_stop == 1u) { accessible = (float)(n_seg_total + seg_excl); goto write_out; }  // every chunk group was decided inside one flush
 
         for (uint32_t ch0 = 0; ch0 < n_chunks; ch0 += NCH) {
             if (!single_group) load_group(ch0);
@@ -275,7 +267,6 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                         base_rank = (uint32_t)__popcll(__ballot(run_ne && seg_excl < seg_i));
                     }
                     const uint32_t round_end = min(n_seg_total, (seg_i & ~255u) + 256u);
-                    if (ABLATE && a.debug_stop == 6u) { accessible += (float)(mword + round_end); goto write_out; }
                     // -- 2. sweep 64 atoms of the flattened runs per iteration: distance rule only.
                     // Lanes past the end look at the atom itself, which the q != p test rejects.
                     while (seg_i < round_end && n_list <= (uint32_t)kListFlush) {
@@ -297,7 +288,6 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                         s_list[w][accept ? n_list + mbcnt64(m) : dummy_slot] = q;
                         n_list += (uint32_t)__popcll(m);
                         seg_i += 64u;
-                        if (stat_sel == 11u) stat++;
                     }
                 } else {
                 if ((seg_i & (uint32_t)(kSegCap - 1)) == 0u) {
@@ -313,7 +303,6 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                         wave_lds_fence();
                     }
                     const uint32_t round_end = min(n_seg_total, (seg_i & ~(uint32_t)(kSegCap - 1)) + (uint32_t)kSegCap);
-                    if (ABLATE && a.debug_stop == 6u) { accessible += (float)(s_seg[w][lane & 31u].x + round_end); goto write_out; }
                     // -- 2. sweep four segments (16 lanes each) per iteration: distance rule only.
                     // Lanes past the end of their segment look at the atom itself, which the
                     // q != p test rejects, so the loop body is branch free.
@@ -337,7 +326,6 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                     // ---- flush: decide points against the queued candidates ----
                     const uint32_t K = n_list;
                     wave_lds_fence();
-                    if (ABLATE && a.debug_stop == 2u) { accessible += (float)(K + s_list[w][lane]); n_list = 0; continue; }
                     // -- 3. prep (lane = candidate): id rule, v, limit; the first pass puts the
                     //       near candidates first
                     uint32_t nA = 0;
@@ -367,17 +355,13 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                         if (live) s_cand[w][slot] = e;
                     }
                     if (lane < 16u) s_cand[w][K + lane] = make_float4(0.f, 0.f, 0.f, neg_inf);  // tile padding
-                    if (stat_sel == 12u) stat += nA;
-                    if (stat_sel == 15u) stat++;
                     wave_lds_fence();
-                    if (ABLATE && a.debug_stop == 3u) { accessible += s_cand[w][lane].w + (float)nA; n_list = 0; continue; }
                     // -- remainder points, scalar rule (lib.rs:185-186,206-207): plain products, `<=`
                     if (do_rem) {
                         // candidate slots past K hold limit = -inf, so whole steps run unchecked
                         unsigned long long mm = 0ull;
                         const float4 *cp = &s_cand[w][rem_grp];
                         const uint32_t steps = (K + rem_groups - 1u) >> (6u - rem_shift);
-                        if (stat_sel == 16u) stat += steps;
                         for (uint32_t st = 0; st < steps; st++) {
                             const float4 cd = *cp;
                             cp += rem_groups;
@@ -395,7 +379,6 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                     // When the whole candidate list is resident (the usual case: one flush), every
                     // chunk group is decided here, so the sweep runs once per atom whatever n_points
                     // is.  Otherwise only the current group is updated and its masks persist.
-                    if (ABLATE && a.debug_stop == 4u) { accessible += (float)__popcll(rem_mask); n_list = 0; continue; }
                     const bool single_flush = last && !flushed;
                     const uint32_t nB = K - nA;
                     uint32_t g0 = ch0;
@@ -430,13 +413,10 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
 #pragma unroll
                             for (int c = 0; c < NCH; c++) occ[c] |= __builtin_amdgcn_ballot_w64(mA[c] > 0.0f);
                         }
-                        if (ABLATE && a.debug_stop == 5u) { acc_fused += (float)__popcll(occ[0] ^ occ[NCH - 1]); g0 += NCH; continue; }
                         // -- 5. phase B: far candidates against the survivors
                         uint32_t S = 0;
 #pragma unroll
                         for (int c = 0; c < NCH; c++) S += (uint32_t)__popcll(~occ[c]);
-                        if (stat_sel == 13u) stat += S;
-                        if (stat_sel == 17u) stat += (nA + 1u) >> 1;
                         if (single_flush && (S == 0u || nB == 0u)) {
                             acc_fused += (float)S;
                         } else if (single_flush && S <= 64u) {
@@ -477,8 +457,6 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                             float mx = neg_inf;
                             const float4 *cp = &s_cand[w][nA + grp];
                             const uint32_t steps = (nB + G - 1u) >> (6u - ps);
-                            if (stat_sel == 14u) stat += steps;
-                            if (stat_sel == 18u) stat += 1u;
                             for (uint32_t st = 0; st < steps; st += 2u) {
                                 const float4 cd = cp[0], ce = cp[G];
                                 cp += 2u * G;
@@ -493,7 +471,6 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
                             wave_lds_fence();
                         } else {
                             // far candidates broadcast against all points of the group, masks exact
-                            if (stat_sel == 19u) stat += K - nA;
                             {
                                 float mB[NCH];
 #pragma unroll
@@ -542,13 +519,12 @@ __global__ __launch_bounds__(256) void k_occlusion_v3(OccArgs3 a)
             if (all_groups) break;
         }
 
-    write_out:
         if (lane == 0) {
             const uint32_t orig = a.sorted_orig[p];
             const float surface_area = (4.0f * 3.14159274101257324219f) * R2;  // 4.0 * PI * r2, lib.rs:220
             const float inv_n = 1.0f / (float)n_points;                        // lib.rs:221
             a.atom_sasa[orig] = surface_area * accessible * inv_n;             // lib.rs:222
-            if (counting) a.neighbor_counts[orig] = stat_sel >= 10u ? stat : k_total;
+            if (counting) a.neighbor_counts[orig] = k_total;
         }
         wave_lds_fence();
     }
