@@ -317,15 +317,152 @@ hipError_t new_stream(rsasa_context *ctx, hipStream_t *out, int level)
 
 int ensure_side_stream(rsasa_context *ctx)
 {
-    if (!ctx->side_stream) RS_HIP(ctx, new_stream(ctx, &ctx->side_stream, 2));
+    if (!ctx->side_stream) RS_HIP(ctx, new_stream(ctx, &ctx->side_stream.h, 2));
     return RSASA_OK;
 }
 
 int ensure_copy_streams(rsasa_context *ctx)
 {
-    if (!ctx->copy_stream) RS_HIP(ctx, new_stream(ctx, &ctx->copy_stream, 1));
-    if (!ctx->d2h_stream) RS_HIP(ctx, new_stream(ctx, &ctx->d2h_stream, 1));
+    if (!ctx->copy_stream) RS_HIP(ctx, new_stream(ctx, &ctx->copy_stream.h, 1));
+    if (!ctx->d2h_stream) RS_HIP(ctx, new_stream(ctx, &ctx->d2h_stream.h, 1));
     return RSASA_OK;
+}
+
+SegmentCount count_segments(const uint32_t *so, size_t S)
+{
+    SegmentCount c;
+    for (size_t s = 0; s < S; s++) {
+        const uint32_t n = so[s + 1] - so[s];
+        c.n_seg += (n + kSegmentAtoms - 1) / kSegmentAtoms;
+        c.n_large += n > kIdAtomsSmall && n <= kIdAtomsLarge;
+        c.has_tail |= n >= kLdsMaxAtoms;
+    }
+    return c;
+}
+
+void write_segments(const uint32_t *so, size_t S, Segment *out, uint32_t *large)
+{
+    for (size_t s = 0; s < S; s++) {
+        const uint32_t b = so[s], e = so[s + 1];
+        if (large && e - b > kIdAtomsSmall && e - b <= kIdAtomsLarge) *large++ = (uint32_t)s;
+        for (uint32_t a = b; a < e; a += kSegmentAtoms)
+            *out++ = Segment{(uint32_t)s, a, std::min(e, a + kSegmentAtoms), a != b ? 1u : 0u};
+    }
+}
+
+}  // namespace rsasa
+
+int rsasa_context::Workspace::reserve_sorted(rsasa_context *ctx, size_t N, size_t cell_words, bool with_id)
+{
+    int rc;
+    has_id = with_id;
+    if ((rc = reserve(ctx, sid_sorted, std::max<size_t>(N, 1) * 4))) return rc;
+    if ((rc = reserve(ctx, rank_of, std::max<size_t>(N, 1) * 4))) return rc;
+    if ((rc = reserve(ctx, cells, cell_words * 4))) return rc;
+    if ((rc = reserve(ctx, sorted_xyzr, std::max<size_t>(N, 1) * 16))) return rc;
+    if ((rc = reserve(ctx, sorted_orig, std::max<size_t>(N, 1) * 4))) return rc;
+    if (has_id && (rc = reserve(ctx, sorted_id32, std::max<size_t>(N, 1) * 4))) return rc;
+    return RSASA_OK;
+}
+
+void rsasa_context::Workspace::sorted_view(BatchView &v) const
+{
+    v.sid_sorted = (uint32_t *)sid_sorted.p;
+    v.cell_of = (uint32_t *)cell_of.p;  // (reserved by reserve_grid for a batch with a tail: batch-wide binning only)
+    v.rank_of = (uint32_t *)rank_of.p;
+    v.cells = (uint32_t *)cells.p;
+    v.sorted_xyzr = (float4 *)sorted_xyzr.p;
+    v.sorted_orig = (uint32_t *)sorted_orig.p;
+    v.sorted_id32 = has_id ? (uint32_t *)sorted_id32.p : nullptr;
+}
+
+int rsasa_context::Workspace::reserve_grid(rsasa_context *ctx, size_t N, size_t S, size_t n_seg_all, uint64_t &capacity, bool has_tail,
+                                           bool with_id)
+{
+    int rc;
+    if (capacity == 0) capacity = std::max<uint64_t>(1u << 16, 20ull * N + 512ull * S);
+    capacity = std::min<uint64_t>(capacity, 0xFFFFFFF0ull);
+    cell_capacity = capacity;
+    // one k_sort_window workgroup per window of kWindowCells 16-bit cell entries (two per entry of the cell
+    // array), at most one partly filled window per structure: whatever fits the cell array fits this list
+    window_capacity = (uint32_t)std::min<uint64_t>(2 * cell_capacity / kWindowCells + S + 1, 0x7FFFFFFFull);
+    if ((rc = reserve(ctx, segments, std::max<size_t>(n_seg_all, 1) * sizeof(Segment)))) return rc;
+    if ((rc = reserve(ctx, acc, std::max<size_t>(S, 1) * sizeof(StructAcc)))) return rc;
+    if ((rc = reserve(ctx, grids, std::max<size_t>(S, 1) * sizeof(StructGrid)))) return rc;
+    if ((rc = reserve(ctx, grid_sums, (std::max<size_t>(S, 1) + 255) / 256 * 32))) return rc;
+    if (has_tail && (rc = reserve(ctx, cell_of, std::max<size_t>(N, 1) * 4))) return rc;  // (batch-wide binning only)
+    if ((rc = reserve(ctx, windows, (size_t)window_capacity * sizeof(uint4)))) return rc;
+    if ((rc = reserve(ctx, scan_sums, kScanBlocks * 4))) return rc;
+    if ((rc = reserve(ctx, status, sizeof(BatchStatus)))) return rc;
+    // + 1 end marker, + 3: k_zero_cells / k_scan_* access whole 16-byte vectors up to the end marker
+    return reserve_sorted(ctx, N, (size_t)(cell_capacity + 1 + 3), with_id);
+}
+
+void rsasa_context::Workspace::grid_view(BatchView &v) const
+{
+    sorted_view(v);
+    v.segments = (const Segment *)segments.p;
+    v.acc = (StructAcc *)acc.p;
+    v.grids = (StructGrid *)grids.p;
+    v.grid_sums = (GridSums *)grid_sums.p;
+    v.cell_capacity = cell_capacity;
+    v.windows = (uint4 *)windows.p;
+    v.window_capacity = window_capacity;
+    v.scan_block_sums = (uint32_t *)scan_sums.p;
+    v.status = (BatchStatus *)status.p;
+}
+
+int rsasa_context::Workspace::reserve_occlusion(rsasa_context *ctx, const Lattice &lat, size_t N, bool with_id, bool bitmaps,
+                                                bool own_values)
+{
+    int rc;
+    // (the matrix-core kernel works on the id folds: no sorted copy of the 64-bit ids then)
+    keep_ids = with_id && !occlusion_uses_mx(ctx->tuning, lat, (uint32_t)N);
+    id_bitmaps = bitmaps;
+    ids_seg_words = bitmaps ? (uint32_t)((N + 2047) / 2048) : 0u;  // (BatchView::ids_seg: a bit per 64 atoms, two bitmaps)
+    own_atom_sasa = own_values;
+    if ((rc = reserve(ctx, deferred_list, std::max<size_t>(N, 1) * 4))) return rc;
+    if ((rc = reserve(ctx, claim, kClaimBytes))) return rc;
+    if (id_bitmaps && (rc = reserve(ctx, ids_seg, 2 * (size_t)ids_seg_words * 4 + 16))) return rc;
+    if (keep_ids && (rc = reserve(ctx, sorted_id, std::max<size_t>(N, 1) * 8))) return rc;
+    if (own_atom_sasa && (rc = reserve(ctx, atom_sasa, std::max<size_t>(N, 1) * 4))) return rc;
+    return RSASA_OK;
+}
+
+void rsasa_context::Workspace::occlusion_view(BatchView &v) const
+{
+    v.deferred_list = (uint32_t *)deferred_list.p;
+    v.claim = (uint32_t *)claim.p;
+    v.ids_seg = id_bitmaps ? (uint32_t *)ids_seg.p : nullptr;
+    v.ids_seg_words = ids_seg_words;
+    v.sorted_id = keep_ids ? (uint64_t *)sorted_id.p : nullptr;
+    if (own_atom_sasa) v.atom_sasa = (float *)atom_sasa.p;
+}
+
+namespace rsasa {
+
+int grid_input_error(rsasa_context *ctx, const BatchStatus &stt)
+{
+    if (stt.grid_too_large)
+        return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "a structure's cell grid exceeds 2^31 cells (coordinates too sparse)");
+    if (stt.bad_input)
+        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "probe_radius + max radius must be a positive finite number");
+    return RSASA_OK;
+}
+
+// the cell array was too small for a batch that needs total_cells: a larger one, three times at the most
+int grid_grow(rsasa_context *ctx, uint64_t total_cells, int attempts, uint64_t &cell_capacity)
+{
+    if (total_cells >= 0xFFFFFFF0ull || attempts >= 3)
+        return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "batch needs more than 2^32 grid cells; split it");
+    cell_capacity = total_cells + total_cells / 8 + 1024;
+    return kGridAgain;
+}
+
+int grid_verdict(rsasa_context *ctx, const BatchStatus &stt, int attempts, uint64_t &cell_capacity)
+{
+    if (const int rc = grid_input_error(ctx, stt)) return rc;
+    return stt.overflow ? grid_grow(ctx, stt.total_cells, attempts, cell_capacity) : RSASA_OK;
 }
 
 int enqueue_batch(rsasa_context *ctx, const Pending &pd, rsasa_context::HostSlot &hs)
@@ -339,75 +476,26 @@ int enqueue_batch(rsasa_context *ctx, const Pending &pd, rsasa_context::HostSlot
     int rc = get_lattice(ctx, pd.n_points, &lat);
     if (rc) return rc;
 
-    // bounds segments: <= kSegmentAtoms atoms of one structure each
-    size_t n_seg = 0;
-    // (behind the segments, in the same upload: the structures whose ids k_ids_distinct's large table takes)
-    size_t n_large = 0;
-    for (size_t s = 0; s < S; s++) {
-        const uint32_t b = bt.structure_offsets_host[s], e = bt.structure_offsets_host[s + 1];
-        n_seg += (e - b + kSegmentAtoms - 1) / kSegmentAtoms;
-        n_large += e - b > kIdAtomsSmall && e - b <= kIdAtomsLarge;
+    const SegmentCount sc = count_segments(bt.structure_offsets_host, S);
+    const size_t n_seg = sc.n_seg, n_large = sc.n_large;
+    const bool has_tail = sc.has_tail;
+    // (behind the segments, in the same upload: the large-id structures' numbers, four per segment-sized entry)
+    const size_t n_seg_all = n_seg + (n_large + 3) / 4;
+    if (n_seg_all * sizeof(Segment) > hs.h_segments.cap) {
+        if (hs.h_segments.p) RS_HIP(ctx, hipStreamSynchronize(pd.stream));
+        RS_HIP(ctx, hs.h_segments.regrow((n_seg_all + n_seg_all / 2 + 64) * sizeof(Segment)));
     }
-    const size_t n_seg_all = n_seg + (n_large + 3) / 4;  // (four structure numbers per segment-sized entry)
-    if (n_seg_all > hs.h_segments_cap) {
-        if (hs.h_segments) {
-            RS_HIP(ctx, hipStreamSynchronize(pd.stream));
-            RS_HIP(ctx, hipHostFree(hs.h_segments));
-            hs.h_segments = nullptr;
-            hs.h_segments_cap = 0;
-        }
-        const size_t cap = n_seg_all + n_seg_all / 2 + 64;
-        RS_HIP(ctx, hipHostMalloc((void **)&hs.h_segments, cap * sizeof(Segment), hipHostMallocDefault));
-        hs.h_segments_cap = cap;
-    }
-    bool has_tail = false;  // some structure is too large for the LDS binning: the batch-wide kernels run too
-    {
-        size_t k = 0, kl = 0;
-        uint32_t *large = reinterpret_cast<uint32_t *>(hs.h_segments + n_seg);
-        for (size_t s = 0; s < S; s++) {
-            const uint32_t b = bt.structure_offsets_host[s], e = bt.structure_offsets_host[s + 1];
-            has_tail |= e - b >= kLdsMaxAtoms;
-            if (e - b > kIdAtomsSmall && e - b <= kIdAtomsLarge) large[kl++] = (uint32_t)s;
-            for (uint32_t a = b; a < e; a += kSegmentAtoms)
-                hs.h_segments[k++] = Segment{(uint32_t)s, a, std::min(e, a + kSegmentAtoms), a != b ? 1u : 0u};
-        }
-    }
-
-    if (ctx->cell_capacity == 0)
-        ctx->cell_capacity = std::max<uint64_t>(1u << 16, 20ull * N + 512ull * S);
-    ctx->cell_capacity = std::min<uint64_t>(ctx->cell_capacity, 0xFFFFFFF0ull);
+    Segment *h_segments = static_cast<Segment *>(hs.h_segments.p);
+    write_segments(bt.structure_offsets_host, S, h_segments, reinterpret_cast<uint32_t *>(h_segments + n_seg));
 
     const bool has_id = bt.id != nullptr;  // (with pd.id32 set, bt.id is the general kernel's device-accessible copy)
-    if ((rc = reserve(ctx, W.segments, std::max<size_t>(n_seg_all, 1) * sizeof(Segment)))) return rc;
-    if ((rc = reserve(ctx, W.acc, std::max<size_t>(S, 1) * sizeof(StructAcc)))) return rc;
-    if ((rc = reserve(ctx, W.grids, std::max<size_t>(S, 1) * sizeof(StructGrid)))) return rc;
-    if ((rc = reserve(ctx, W.grid_sums, (std::max<size_t>(S, 1) + 255) / 256 * 32))) return rc;
-    if ((rc = reserve(ctx, W.sid_sorted, std::max<size_t>(N, 1) * 4))) return rc;
-    if ((rc = reserve(ctx, W.deferred_list, std::max<size_t>(N, 1) * 4))) return rc;
-    if ((rc = reserve(ctx, W.claim, kClaimBytes))) return rc;
-    const size_t ids_seg_words = (N + 2047) / 2048;  // (BatchView::ids_seg: a bit per 64 atoms, two bitmaps)
-    if (has_id && (rc = reserve(ctx, W.ids_seg, 2 * ids_seg_words * 4 + 16))) return rc;
-    if (has_tail && (rc = reserve(ctx, W.cell_of, std::max<size_t>(N, 1) * 4))) return rc;  // (batch-wide binning only)
-    if ((rc = reserve(ctx, W.rank_of, std::max<size_t>(N, 1) * 4))) return rc;
-    // + 1 end marker, + 3: k_zero_cells / k_scan_* access whole 16-byte vectors up to the end marker
-    if ((rc = reserve(ctx, W.cells, (size_t)(ctx->cell_capacity + 1 + 3) * 4))) return rc;
-    // one k_sort_window workgroup per window of kWindowCells 16-bit cell entries (two per entry of the cell
-    // array), at most one partly filled window per structure: whatever fits the cell array fits this list
-    const uint64_t window_capacity = std::min<uint64_t>(2 * ctx->cell_capacity / kWindowCells + S + 1, 0x7FFFFFFFull);
-    if ((rc = reserve(ctx, W.windows, (size_t)window_capacity * sizeof(uint4)))) return rc;
-    if ((rc = reserve(ctx, W.scan_sums, kScanBlocks * 4))) return rc;
-    if ((rc = reserve(ctx, W.sorted_xyzr, std::max<size_t>(N, 1) * 16))) return rc;
-    if ((rc = reserve(ctx, W.sorted_orig, std::max<size_t>(N, 1) * 4))) return rc;
-    // (the matrix-core kernel works on the id folds: no sorted copy of the 64-bit ids then)
-    const bool keep_ids = has_id && !occlusion_uses_mx(ctx->tuning, lat, (uint32_t)N);
+    if ((rc = W.reserve_grid(ctx, N, S, n_seg_all, ctx->cell_capacity, has_tail, has_id))) return rc;
+    if ((rc = W.reserve_occlusion(ctx, lat, N, has_id, has_id, !bt.out_atom_sasa))) return rc;
+    const bool keep_ids = W.keep_ids;
     if (keep_ids && pd.id32) return fail(ctx, RSASA_ERR_INTERNAL, "folded ids on a batch the per-atom kernels take");
-    if (keep_ids && (rc = reserve(ctx, W.sorted_id, std::max<size_t>(N, 1) * 8))) return rc;
-    if (has_id && (rc = reserve(ctx, W.sorted_id32, std::max<size_t>(N, 1) * 4))) return rc;
-    if ((rc = reserve(ctx, W.status, sizeof(BatchStatus)))) return rc;
-    if (!bt.out_atom_sasa && (rc = reserve(ctx, W.atom_sasa, std::max<size_t>(N, 1) * 4))) return rc;
 
     if (n_seg_all)
-        RS_HIP(ctx, hipMemcpyAsync(W.segments.p, hs.h_segments, n_seg_all * sizeof(Segment),
+        RS_HIP(ctx, hipMemcpyAsync(W.segments.p, h_segments, n_seg_all * sizeof(Segment),
                                    hipMemcpyHostToDevice, st));
 
     BatchView v{};
@@ -428,28 +516,9 @@ int enqueue_batch(rsasa_context *ctx, const Pending &pd, rsasa_context::HostSlot
     v.n_atoms = (uint32_t)N; v.n_structures = (uint32_t)S; v.n_residues = (uint32_t)R;
     v.n_segments = (uint32_t)n_seg;
     v.probe = pd.probe;
-    v.segments = (const Segment *)W.segments.p;
-    v.acc = (StructAcc *)W.acc.p;
-    v.grids = (StructGrid *)W.grids.p;
-    v.grid_sums = (GridSums *)W.grid_sums.p;
-    v.sid_sorted = (uint32_t *)W.sid_sorted.p;
-    v.deferred_list = (uint32_t *)W.deferred_list.p;
-    v.claim = (uint32_t *)W.claim.p;
-    v.ids_seg = has_id ? (uint32_t *)W.ids_seg.p : nullptr;
-    v.ids_seg_words = (uint32_t)ids_seg_words;
-    v.cell_of = (uint32_t *)W.cell_of.p;
-    v.rank_of = (uint32_t *)W.rank_of.p;
-    v.cells = (uint32_t *)W.cells.p;
-    v.cell_capacity = ctx->cell_capacity;
-    v.windows = (uint4 *)W.windows.p;
-    v.window_capacity = (uint32_t)window_capacity;
-    v.scan_block_sums = (uint32_t *)W.scan_sums.p;
-    v.sorted_xyzr = (float4 *)W.sorted_xyzr.p;
-    v.sorted_orig = (uint32_t *)W.sorted_orig.p;
-    v.sorted_id = keep_ids ? (uint64_t *)W.sorted_id.p : nullptr;
-    v.sorted_id32 = has_id ? (uint32_t *)W.sorted_id32.p : nullptr;
-    v.status = (BatchStatus *)W.status.p;
-    v.atom_sasa = bt.out_atom_sasa ? bt.out_atom_sasa : (float *)W.atom_sasa.p;
+    v.atom_sasa = bt.out_atom_sasa;
+    W.grid_view(v);
+    W.occlusion_view(v);
     v.residue_sasa = (R && bt.residue_offsets) ? bt.out_residue_sasa : nullptr;
     v.neighbor_counts = bt.out_neighbor_counts;
 
@@ -497,7 +566,7 @@ int enqueue_batch(rsasa_context *ctx, const Pending &pd, rsasa_context::HostSlot
     if (ctx->timing) RS_HIP(ctx, hipEventRecord(W.ev[3], st));
     launch_residue_sums(v, st);
     if (ctx->timing) RS_HIP(ctx, hipEventRecord(W.ev[4], st));
-    RS_HIP(ctx, hipMemcpyAsync(hs.h_status, W.status.p, sizeof(BatchStatus),
+    RS_HIP(ctx, hipMemcpyAsync(hs.h_status.p, W.status.p, sizeof(BatchStatus),
                                hipMemcpyDeviceToHost, st));
     RS_HIP(ctx, hipGetLastError());
     return RSASA_OK;
@@ -514,60 +583,44 @@ int wait_one(rsasa_context *ctx, Pending &pd)
             pd.active = false;
             return fail(ctx, RSASA_ERR_HIP, "hipStreamSynchronize", e);
         }
-        const BatchStatus stt = *ctx->slot[pd.ws].h_status;
-        if (stt.grid_too_large) {
-            pd.active = false;
-            return fail(ctx, RSASA_ERR_GRID_TOO_LARGE,
-                        "a structure's cell grid exceeds 2^31 cells (coordinates too sparse)");
-        }
-        if (stt.bad_input) {
-            pd.active = false;
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT,
-                        "probe_radius + max radius must be a positive finite number");
-        }
-        if (!stt.overflow && ctx->slot[pd.ws].ids_check && (stt.ids_unordered & 2u) != 0u && pd.attempts < 3) {
-            // the batch's one occlusion launch was the id-less instantiation and the ids do matter (OcclusionChain::solo):
-            // nothing was computed - the batch runs again, with its ids and without the check
+        const BatchStatus stt = ctx->slot[pd.ws].status();
+        int rc = grid_verdict(ctx, stt, pd.attempts, ctx->cell_capacity);
+        // the batch's one occlusion launch was the id-less instantiation and the ids do matter (OcclusionChain::solo):
+        // nothing was computed
+        const bool solo_missed = rc == RSASA_OK && ctx->slot[pd.ws].ids_check && (stt.ids_unordered & 2u) != 0u;
+        if (rc == kGridAgain) {
+            pd.attempts++;  // the cell array was too small for this batch: it has grown, run again
+        } else if (solo_missed && pd.solo_ok) {
+            // the batch runs again with its ids, as a launch pair (the check runs with it).  Only the solo launch raises
+            // the bit: once per batch, whatever the cell array's attempts
             ctx->ids_drop_hint = false;
             ctx->ids_unordered_hint = (stt.ids_unordered & 1u) != 0u;
-            pd.solo_ok = false;  // (as a pair this time: every structure in the instantiation that is its own)
-            pd.attempts++;
-            int rc = enqueue_batch(ctx, pd, ctx->slot[pd.ws]);
-            if (rc) {
-                pd.active = false;
-                return rc;
-            }
-            continue;
-        }
-        if (!stt.overflow) {
-            ctx->tuning.deferred_hint = stt.deferred;  // (sizes the next batch's launch over its deferred list)
-            if (ctx->slot[pd.ws].ids_check) {
-                ctx->ids_drop_hint = !stt.ids_needed;
-                ctx->ids_unordered_hint = (stt.ids_unordered & 1u) != 0u;
-                ctx->ids_kept_structures.store(stt.ids_needed, std::memory_order_relaxed);
-                if (!stt.ids_needed) ctx->ids_dropped.fetch_add(1, std::memory_order_relaxed);
-            }
-            if (ctx->timing) {
-                float g = 0, o = 0, a = 0, t = 0;
-                (void)hipEventElapsedTime(&g, W.ev[0], W.ev[1]);
-                (void)hipEventElapsedTime(&o, W.ev[2], W.ev[3]);
-                (void)hipEventElapsedTime(&a, W.ev[3], W.ev[4]);
-                (void)hipEventElapsedTime(&t, W.ev[0], W.ev[4]);
-                ctx->timings = rsasa_timings_t{g, o, a, t, stt.grid_cells, pd.batch.n_atoms, stt.deferred};
-                ctx->timings_valid = true;
+            pd.solo_ok = false;  // (every structure in the instantiation that is its own)
+        } else {
+            if (solo_missed) {
+                rc = fail(ctx, RSASA_ERR_INTERNAL, "a launch pair reports the id-less launch's verdict");
+            } else if (rc == RSASA_OK) {
+                ctx->tuning.deferred_hint = stt.deferred;  // (sizes the next batch's launch over its deferred list)
+                if (ctx->slot[pd.ws].ids_check) {
+                    ctx->ids_drop_hint = !stt.ids_needed;
+                    ctx->ids_unordered_hint = (stt.ids_unordered & 1u) != 0u;
+                    ctx->ids_kept_structures.store(stt.ids_needed, std::memory_order_relaxed);
+                    if (!stt.ids_needed) ctx->ids_dropped.fetch_add(1, std::memory_order_relaxed);
+                }
+                if (ctx->timing) {
+                    float g = 0, o = 0, a = 0, t = 0;
+                    (void)hipEventElapsedTime(&g, W.ev[0], W.ev[1]);
+                    (void)hipEventElapsedTime(&o, W.ev[2], W.ev[3]);
+                    (void)hipEventElapsedTime(&a, W.ev[3], W.ev[4]);
+                    (void)hipEventElapsedTime(&t, W.ev[0], W.ev[4]);
+                    ctx->timings = rsasa_timings_t{g, o, a, t, stt.grid_cells, pd.batch.n_atoms, stt.deferred};
+                    ctx->timings_valid = true;
+                }
             }
             pd.active = false;
-            return RSASA_OK;
+            return rc;
         }
-        // the cell array was too small for this batch: grow and run again
-        if (stt.total_cells >= 0xFFFFFFF0ull || pd.attempts >= 3) {
-            pd.active = false;
-            return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "batch needs more than 2^32 grid cells; split it");
-        }
-        ctx->cell_capacity = stt.total_cells + stt.total_cells / 8 + 1024;
-        pd.attempts++;
-        int rc = enqueue_batch(ctx, pd, ctx->slot[pd.ws]);
-        if (rc) {
+        if ((rc = enqueue_batch(ctx, pd, ctx->slot[pd.ws]))) {
             pd.active = false;
             return rc;
         }
@@ -671,20 +724,20 @@ int rsasa::context_create(int device, int own_queues, rsasa_context_t **out_ctx)
     ctx->node = device_node_cpus(device);
     DeviceGuard guard(device);
     hipError_t e = guard.err;
-    if (e == hipSuccess) e = new_stream(ctx, &ctx->stream, 2);
+    if (e == hipSuccess) e = new_stream(ctx, &ctx->stream.h, 2);
     for (int w = 0; w < rsasa_context::kInFlight; w++) {
-        for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipEventCreate(&ctx->ws[w].ev[i]);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ws[w].ev_occ, hipEventDisableTiming);
+        for (int i = 0; i < 5 && e == hipSuccess; i++) e = hipEventCreate(&ctx->ws[w].ev[i].h);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ws[w].ev_occ.h, hipEventDisableTiming);
     }
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_link, hipEventDisableTiming);
-    for (int i = 0; i < rsasa_context::kSlots && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ctx->ev_copy[i], hipEventDisableTiming);
-    for (int i = 0; i < rsasa_context::kSlots && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ctx->ev_d2h[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_fork.h, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_join.h, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_link.h, hipEventDisableTiming);
+    for (int i = 0; i < rsasa_context::kSlots && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ctx->ev_copy[i].h, hipEventDisableTiming);
+    for (int i = 0; i < rsasa_context::kSlots && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ctx->ev_d2h[i].h, hipEventDisableTiming);
     for (int i = 0; i < rsasa_context::kSlots && e == hipSuccess; i++) {
-        e = hipHostMalloc((void **)&ctx->slot[i].h_status, sizeof(BatchStatus), hipHostMallocDefault);
-        if (e == hipSuccess) std::memset(ctx->slot[i].h_status, 0, sizeof(BatchStatus));
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_done[i], hipEventDisableTiming);
+        e = ctx->slot[i].h_status.regrow(sizeof(BatchStatus));
+        if (e == hipSuccess) std::memset(ctx->slot[i].h_status.p, 0, sizeof(BatchStatus));
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ctx->ev_done[i].h, hipEventDisableTiming);
     }
     if (e != hipSuccess) {
         rsasa_context_destroy(ctx);
@@ -721,61 +774,14 @@ int rsasa_context_destroy(rsasa_context_t *ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
     if (ctx->d2h_stream) (void)hipStreamSynchronize(ctx->d2h_stream);
-    for (DeviceBuffer *b : {&ctx->segments, &ctx->acc, &ctx->grids, &ctx->grid_sums, &ctx->sid_sorted, &ctx->deferred_list, &ctx->cell_of,
-                            &ctx->rank_of, &ctx->cells, &ctx->windows, &ctx->scan_sums, &ctx->sorted_xyzr,
-                            &ctx->sorted_orig, &ctx->sorted_id, &ctx->sorted_id32, &ctx->status, &ctx->atom_sasa, &ctx->claim, &ctx->ws[0].ids_seg,
-                            &ctx->in_x, &ctx->in_y, &ctx->in_z, &ctx->in_r, &ctx->in_id,
-                            &ctx->in_res, &ctx->out_res, &ctx->out_k, &ctx->small_in, &ctx->small_out, &ctx->tr_xyz, &ctx->tr_r,
-                            &ctx->tr_id, &ctx->tr_res})
-        release(*b);
-    for (DeviceBuffer &b : ctx->in_pack) release(b);
-    neighbors_release(ctx);
-    for (auto &m : ctx->more)
-        for (DeviceBuffer *b : {&m.x, &m.y, &m.z, &m.r, &m.id, &m.res, &m.atom_sasa, &m.out_res}) release(*b);
-    // (the coding pool is the device's, shared by its contexts: it stays)
-    if (ctx->h_pack) (void)hipHostFree(ctx->h_pack);
-    for (auto &kv : ctx->lattices)
-        if (kv.second.d) (void)hipFree(kv.second.d);
-    for (int i = 0; i < rsasa_context::kSlots; i++) {
-        if (ctx->slot[i].h_segments) (void)hipHostFree(ctx->slot[i].h_segments);
-        if (ctx->slot[i].h_status) (void)hipHostFree(ctx->slot[i].h_status);
-        if (ctx->slot[i].h_res) (void)hipHostFree(ctx->slot[i].h_res);
-        if (ctx->ev_done[i]) (void)hipEventDestroy(ctx->ev_done[i]);
-    }
-    for (int w = 0; w < rsasa_context::kInFlight; w++) {
-        for (int i = 0; i < 5; i++)
-            if (ctx->ws[w].ev[i]) (void)hipEventDestroy(ctx->ws[w].ev[i]);
-        if (ctx->ws[w].ev_occ) (void)hipEventDestroy(ctx->ws[w].ev_occ);
-    }
-    {
-        rsasa_context::Workspace &w1 = ctx->ws[1];
-        for (DeviceBuffer *b : {&w1.segments, &w1.acc, &w1.grids, &w1.grid_sums, &w1.sid_sorted, &w1.deferred_list, &w1.cell_of, &w1.rank_of,
-                                &w1.cells, &w1.windows, &w1.scan_sums, &w1.sorted_xyzr, &w1.sorted_orig, &w1.sorted_id, &w1.sorted_id32,
-                                &w1.status, &w1.atom_sasa, &w1.claim, &w1.ids_seg})
-            release(*b);
-    }
-    if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
-    for (int i = 0; i < rsasa_context::kSlots; i++)
-        if (ctx->ev_copy[i]) (void)hipEventDestroy(ctx->ev_copy[i]);
-    for (int i = 0; i < rsasa_context::kSlots; i++) {
-        if (ctx->ev_d2h[i]) (void)hipEventDestroy(ctx->ev_d2h[i]);
-        if (ctx->h_out[i]) (void)hipHostFree(ctx->h_out[i]);
-    }
-    if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-    if (ctx->d2h_stream) (void)hipStreamDestroy(ctx->d2h_stream);
-    if (ctx->h_small) (void)hipHostFree(ctx->h_small);
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
     if (ctx->device >= 0 && ctx->device < 64) {
         std::lock_guard<std::mutex> lk(g_link[ctx->device].mu);
         if (g_link[ctx->device].owner == ctx) { g_link[ctx->device].last = nullptr; g_link[ctx->device].owner = nullptr; }
     }
-    if (ctx->ev_link) (void)hipEventDestroy(ctx->ev_link);
-    for (auto &row : ctx->tr_ev)
-        for (hipEvent_t e : row)
-            if (e) (void)hipEventDestroy(e);
-    if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    for (auto &kv : ctx->lattices)
+        if (kv.second.d) (void)hipFree(kv.second.d);
+    // (the coding pool is the device's, shared by its contexts: it stays.  Everything else is the members' own to free,
+    // here, while the guard keeps the context's device current)
     delete ctx;
     return RSASA_OK;
 }
@@ -926,7 +932,7 @@ int rsasa::batch_enqueue(rsasa_context *ctx, const rsasa_device_batch_t *batch, 
         if ((rc = wait_oldest(ctx))) return rc;
     const int w = ctx->n_pending ? ctx->pending[ctx->head].ws ^ 1 : 0;
     if (w == 1 && !hip_stream && !ctx->stream2)
-        RS_HIP(ctx, new_stream(ctx, &ctx->stream2, 2));
+        RS_HIP(ctx, new_stream(ctx, &ctx->stream2.h, 2));
     Pending &pd = ctx->pending[ctx->head ^ (ctx->n_pending ? 1 : 0)];
     pd = Pending{};
     pd.batch = *batch;
@@ -996,20 +1002,20 @@ int rsasa_segment_sums(rsasa_context_t *ctx, const float *values, size_t n_value
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     RS_DEVICE(ctx);
     if (ctx->n_pending && (rc = wait_pending(ctx))) return rc;
-    if ((rc = reserve(ctx, ctx->atom_sasa, std::max<size_t>(n_values, 1) * 4))) return rc;
+    if ((rc = reserve(ctx, ctx->ws[0].atom_sasa, std::max<size_t>(n_values, 1) * 4))) return rc;
     if ((rc = reserve(ctx, ctx->in_res, (n_segments + 1) * 4))) return rc;
     if ((rc = reserve(ctx, ctx->out_res, n_segments * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->status, sizeof(BatchStatus)))) return rc;
+    if ((rc = reserve(ctx, ctx->ws[0].status, sizeof(BatchStatus)))) return rc;
     hipStream_t st = ctx->stream;
-    RS_HIP(ctx, hipMemsetAsync(ctx->status.p, 0, sizeof(BatchStatus), st));
+    RS_HIP(ctx, hipMemsetAsync(ctx->ws[0].status.p, 0, sizeof(BatchStatus), st));
     if (n_values)
-        RS_HIP(ctx, hipMemcpyAsync(ctx->atom_sasa.p, values, n_values * 4, hipMemcpyHostToDevice, st));
+        RS_HIP(ctx, hipMemcpyAsync(ctx->ws[0].atom_sasa.p, values, n_values * 4, hipMemcpyHostToDevice, st));
     RS_HIP(ctx, hipMemcpyAsync(ctx->in_res.p, offsets, (n_segments + 1) * 4, hipMemcpyHostToDevice, st));
     BatchView v{};
     v.residue_offsets = (const uint32_t *)ctx->in_res.p;
     v.n_residues = (uint32_t)n_segments;
-    v.status = (BatchStatus *)ctx->status.p;
-    v.atom_sasa = (float *)ctx->atom_sasa.p;
+    v.status = (BatchStatus *)ctx->ws[0].status.p;
+    v.atom_sasa = (float *)ctx->ws[0].atom_sasa.p;
     v.residue_sasa = (float *)ctx->out_res.p;
     launch_residue_sums(v, st);
     RS_HIP(ctx, hipMemcpyAsync(out, ctx->out_res.p, n_segments * 4, hipMemcpyDeviceToHost, st));

@@ -33,9 +33,54 @@ namespace rsasa {
 const char *tuning_env(const char *name);  // an RSASA_* measurement switch, read only under RSASA_TUNING=1 (context.cpp)
 void generate_sphere_points(size_t n, float *x, float *y, float *z);
 
-struct DeviceBuffer {
+// ---- owners of what a context allocates: a handle, a destructor that frees it, move-only ----
+struct DeviceBuffer;
+void release(DeviceBuffer &b);
+struct DeviceBuffer {  // device memory, grown by reserve()
     void *p = nullptr;
     size_t cap = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DeviceBuffer() { release(*this); }
+};
+struct PinnedBlock {  // page-locked host memory; cap in bytes (0 where nobody asks)
+    void *p = nullptr;
+    size_t cap = 0;
+    PinnedBlock() = default;
+    PinnedBlock(PinnedBlock &&o) noexcept : p(std::exchange(o.p, nullptr)), cap(std::exchange(o.cap, 0)) {}
+    PinnedBlock &operator=(PinnedBlock &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~PinnedBlock() { if (p) (void)hipHostFree(p); }
+    // a new block of `bytes` in place of the old one (contents are NOT preserved; the caller has drained whatever reads it)
+    hipError_t regrow(size_t bytes)
+    {
+        if (p) {
+            const hipError_t e = hipHostFree(p);
+            if (e != hipSuccess) return e;
+            p = nullptr;
+            cap = 0;
+        }
+        const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) p = nullptr;
+        else cap = bytes;
+        return e;
+    }
+};
+struct Event {
+    hipEvent_t h = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Event &operator=(Event &&o) noexcept { std::swap(h, o.h); return *this; }
+    ~Event() { if (h) (void)hipEventDestroy(h); }
+    operator hipEvent_t() const { return h; }
+};
+struct Stream {
+    hipStream_t h = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Stream &operator=(Stream &&o) noexcept { std::swap(h, o.h); return *this; }
+    ~Stream() { if (h) (void)hipStreamDestroy(h); }
+    operator hipStream_t() const { return h; }
 };
 
 // CPUs of the NUMA node a GPU hangs off, from sysfs (numa_node / local_cpulist of its PCI address).  `valid` only on
@@ -290,10 +335,13 @@ struct HostStream {
 
 using namespace rsasa;
 
+// Every device buffer, pinned block, event and stream below is an owner (DeviceBuffer, PinnedBlock, Event, Stream) that
+// frees its handle when the context is deleted.  rsasa_context_destroy drains the streams first and deletes the context
+// with its device current; after that no free needs a live stream, so the order of the members carries no meaning.
 struct rsasa_context {
     int device = 0;
     NodeCpus node;                                // CPUs of the GPU's NUMA node (valid on multi-node hosts only)
-    hipStream_t stream = nullptr;
+    Stream stream;
     std::recursive_mutex mu;
     std::string last_error;
     int simd_width = 8;
@@ -301,8 +349,8 @@ struct rsasa_context {
     bool small_path = true;                       // RSASA_SMALL_PATH=0: small host batches take the general path too
     bool overlap_tail = false;                    // RSASA_OVERLAP_TAIL=1: bin the tail on the side stream, next to the first
                                                   // occlusion launch (only batches with a structure of 65 536 atoms or more have a tail now)
-    hipStream_t side_stream = nullptr;            // runs the tail's binning next to the launch stream
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    Stream side_stream;                           // runs the tail's binning next to the launch stream
+    Event ev_fork, ev_join;
     rsasa_timings_t timings{};
     bool timings_valid = false;
 
@@ -311,20 +359,36 @@ struct rsasa_context {
     // tail of the occlusion kernel at the end of a batch then overlap with its neighbour's.  Host slot w serves
     // workspace w.  Everything else (host-pointer entry points, sub-batches of the pipelined host path) runs in
     // workspace 0.
+    //
+    // A batch's set-up is written once, here: reserve_* size the buffers of one part of the pipeline for a batch and
+    // remember what they were sized for, the *_view of the same name points a BatchView at them.  The general path
+    // (enqueue_batch) uses all three parts, the neighbour calls the grid, the small path - whose grids, windows and
+    // status live in its staging block - the sorted atoms and the occlusion part.
     struct Workspace {
         DeviceBuffer segments, acc, grids, grid_sums, sid_sorted, deferred_list, cell_of, rank_of, cells, windows, scan_sums,
             sorted_xyzr, sorted_orig, sorted_id, sorted_id32, status, atom_sasa, claim, ids_seg;
-        hipEvent_t ev[5] = {};  // timing (rsasa_context_enable_timing): start, grid built, occlusion starts / has run, sums done
-        hipEvent_t ev_occ = nullptr;  // the batch's occlusion kernels have run (the other workspace's batch starts its own
+        Event ev[5];            // timing (rsasa_context_enable_timing): start, grid built, occlusion starts / has run, sums done
+        Event ev_occ;                 // the batch's occlusion kernels have run (the other workspace's batch starts its own
         bool occ_recorded = false;    // behind it: two occlusion kernels sharing the CUs only slow each other down)
+        // what the last reserve_* calls sized the buffers for (the *_view functions pass it on)
+        uint64_t cell_capacity = 0;
+        uint32_t window_capacity = 0, ids_seg_words = 0;
+        bool has_id = false, keep_ids = false, id_bitmaps = false, own_atom_sasa = false;
+
+        // the cell-sorted atoms and the cell array (`cell_words` entries) that the binning kernels fill
+        int reserve_sorted(rsasa_context *ctx, size_t N, size_t cell_words, bool has_id);
+        void sorted_view(BatchView &v) const;
+        // everything the three grid kernels (prepare, LDS binning, tail binning) touch, the sorted atoms included.
+        // cell_capacity: the caller's size of the cell array (0: chosen here from N and S), which grid_verdict grows
+        int reserve_grid(rsasa_context *ctx, size_t N, size_t S, size_t n_seg_all, uint64_t &cell_capacity, bool has_tail, bool has_id);
+        void grid_view(BatchView &v) const;  // (cell_capacity and window_capacity too)
+        // what only the occlusion launch needs.  id_bitmaps: BatchView::ids_seg; own_atom_sasa: the caller gave no array for
+        // the values.  keep_ids (a sorted copy of the 64-bit ids: the per-atom kernels read them) is decided here
+        int reserve_occlusion(rsasa_context *ctx, const Lattice &lat, size_t N, bool has_id, bool id_bitmaps, bool own_atom_sasa);
+        void occlusion_view(BatchView &v) const;
     } ws[2];
     static constexpr int kInFlight = 2;
-    hipStream_t stream2 = nullptr;                // launch stream of workspace 1 (created by the first overlapped enqueue)
-    DeviceBuffer &segments = ws[0].segments, &acc = ws[0].acc, &grids = ws[0].grids, &grid_sums = ws[0].grid_sums,
-                 &sid_sorted = ws[0].sid_sorted, &deferred_list = ws[0].deferred_list, &cell_of = ws[0].cell_of,
-                 &rank_of = ws[0].rank_of, &cells = ws[0].cells, &windows = ws[0].windows, &scan_sums = ws[0].scan_sums,
-                 &sorted_xyzr = ws[0].sorted_xyzr, &sorted_orig = ws[0].sorted_orig, &sorted_id = ws[0].sorted_id,
-                 &sorted_id32 = ws[0].sorted_id32, &status = ws[0].status, &atom_sasa = ws[0].atom_sasa, &claim = ws[0].claim;
+    Stream stream2;                               // launch stream of workspace 1 (created by the first overlapped enqueue)
     // staging for the host-pointer entry points (device)
     DeviceBuffer in_x, in_y, in_z, in_r, in_id, in_res, out_res, out_k;
     // Further input / output slots of the pipelined host-buffer path: a slot per sub-batch of a call (kSlots >= the
@@ -339,45 +403,41 @@ struct rsasa_context {
     // folded ids, radius codes - sits in ONE pinned block per sub-batch and crosses the link in ONE copy (every
     // copy costs the link about 12 us of idle time).
     DeviceBuffer in_pack[kSlots];                 // that block of the sub-batch in slot k, on the device
-    char *h_pack = nullptr;                       // pinned: the blocks of a whole host batch
-    size_t h_pack_cap = 0;
+    PinnedBlock h_pack;                           // the blocks of a whole host batch
     FoldPool *fold_pool = nullptr;                // the device's shared coding pool (first large host call; never owned)
     RadiusCodec radius_codec;
-    hipStream_t copy_stream = nullptr;            // H2D of the next sub-batch while the current one computes
-    hipStream_t d2h_stream = nullptr;             // D2H of the previous sub-batch's results meanwhile
-    hipEvent_t ev_copy[kSlots] = {};
-    hipEvent_t ev_d2h[kSlots] = {};               // output slot k has been copied out
-    void *h_out[kSlots] = {};                     // pinned staging for results whose destination is pageable
-    size_t h_out_cap[kSlots] = {};
+    Stream copy_stream;                           // H2D of the next sub-batch while the current one computes
+    Stream d2h_stream;                            // D2H of the previous sub-batch's results meanwhile
+    Event ev_copy[kSlots];
+    Event ev_d2h[kSlots];                         // output slot k has been copied out
+    PinnedBlock h_out[kSlots];                    // staging for results whose destination is pageable
     DeviceBuffer small_in, small_out;          // small host batches: one upload / one download buffer
-    void *h_small = nullptr;                   // pinned staging of the same layout
-    size_t h_small_cap = 0;
+    PinnedBlock h_small;                       // staging of the same layout
     DeviceBuffer tr_xyz, tr_r, tr_id, tr_res;  // trajectory staging (frame-major xyz, per-topology columns)
-    // pinned host
     // Host side of one enqueued batch (pinned): its bounds segments (source of an async upload) and
     // the status block the device writes back.  Slot 0 serves the batch entry points; the pipelined
     // host-buffer path keeps two sub-batches in flight and alternates between slots 0 and 1.
     struct HostSlot {
-        Segment *h_segments = nullptr;
-        size_t h_segments_cap = 0;
-        BatchStatus *h_status = nullptr;
-        uint32_t *h_res = nullptr;      // rebased residue offsets of a sub-batch (a pageable source would
-        size_t h_res_cap = 0;           // make the "asynchronous" upload wait for the copy stream)
+        PinnedBlock h_segments;         // Segment entries
+        PinnedBlock h_status;           // one BatchStatus
+        PinnedBlock h_res;              // rebased residue offsets of a sub-batch (a pageable source would
+                                        // make the "asynchronous" upload wait for the copy stream)
+        const BatchStatus &status() const { return *static_cast<const BatchStatus *>(h_status.p); }
         bool ids_check = false;         // the batch that last used the slot ran with BatchView::ids_check
     } slot[kSlots];
     std::atomic<uint64_t> ids_dropped{0};         // batches / sub-batches that ran without their ids (rsasa_context_ids_dropped)
     std::atomic<uint64_t> ids_kept_structures{0}; // structures of the last checked (sub-)batch that kept their ids (rsasa_context_ids_kept)
     bool ids_drop_hint = true;                    // what the last checked batch did (OcclusionChain::expect_ids_dropped)
     bool ids_unordered_hint = false;              // its ids were in no order: the next batch brings the id tables (BatchView::ids_tables)
-    hipEvent_t ev_done[kSlots] = {};              // all work of the sub-batch in slot k has been executed
+    Event ev_done[kSlots];                        // all work of the sub-batch in slot k has been executed
     uint64_t cell_capacity = 0;
 
     std::map<std::pair<size_t, int>, LatticeEntry> lattices;
     Pending pending[2];   // device batches in flight, oldest first: pending[head], pending[head ^ 1]
     int head = 0, n_pending = 0;
     OcclusionTuning tuning;
-    hipEvent_t ev_link = nullptr;  // recorded behind the last upload of a pipelined host call (LinkTurn)
-    hipEvent_t tr_ev[8][4] = {};   // RSASA_H2H_TRACE: a sub-batch's uploads and kernels, start and end
+    Event ev_link;                 // recorded behind the last upload of a pipelined host call (LinkTurn)
+    Event tr_ev[8][4];             // RSASA_H2H_TRACE: a sub-batch's uploads and kernels, start and end
     LinkGate *link_gate = nullptr; // a worker context of a stream of host batches: the calls take the link in ticket order
     uint64_t link_ticket = 0;
     int own_queues = 0;            // 1: the copy streams, 2: every stream on a hardware queue of its own (new_stream)
@@ -388,7 +448,7 @@ struct rsasa_context {
     // neither waited for nor disturbed; the calls queue their work on `stream` behind whatever it holds
     Workspace nb_ws;
     DeviceBuffer nb_x, nb_y, nb_z, nb_r, nb_id, nb_map, nb_counts, nb_offsets, nb_parts, nb_info, nb_entries, nb_spill, nb_recs;
-    void *nb_host = nullptr;       // pinned: the BatchStatus and NbInfo of the last neighbour call
+    PinnedBlock nb_host;           // the BatchStatus and NbInfo of the last neighbour call
     uint64_t nb_cell_capacity = 0;
 };
 
@@ -486,18 +546,32 @@ struct LinkHold {
 };
 
 int reserve(rsasa_context *ctx, DeviceBuffer &b, size_t bytes);  // grows `b` (contents are NOT preserved)
-void release(DeviceBuffer &b);
 int get_lattice(rsasa_context *ctx, size_t n_points, Lattice *out);
 hipError_t new_stream(rsasa_context *ctx, hipStream_t *out, int level);
 int ensure_side_stream(rsasa_context *ctx);
 int ensure_copy_streams(rsasa_context *ctx);
+// A batch's bounds segments: <= kSegmentAtoms atoms of one structure each.  n_large: the structures whose ids
+// k_ids_distinct's large table takes; has_tail: some structure is too large for the LDS binning (the batch-wide kernels run too)
+struct SegmentCount {
+    size_t n_seg = 0, n_large = 0;
+    bool has_tail = false;
+};
+SegmentCount count_segments(const uint32_t *structure_offsets, size_t S);
+// writes the n_seg entries to `out` and, if `large` is set, the n_large structures' numbers there
+void write_segments(const uint32_t *structure_offsets, size_t S, Segment *out, uint32_t *large);
+// What the grid kernels' BatchStatus says: RSASA_OK - the grid stands; kGridAgain (positive: not an error) - the cell
+// array was too small, cell_capacity has grown, run again (`attempts` runs have been made again already); else the error.
+constexpr int kGridAgain = 3;
+int grid_verdict(rsasa_context *ctx, const BatchStatus &stt, int attempts, uint64_t &cell_capacity);
+// (its two halves, for a call that looks at several sub-batches before it decides: HostBatch::run_piped)
+int grid_input_error(rsasa_context *ctx, const BatchStatus &stt);
+int grid_grow(rsasa_context *ctx, uint64_t total_cells, int attempts, uint64_t &cell_capacity);
 int enqueue_batch(rsasa_context *ctx, const Pending &pd, rsasa_context::HostSlot &hs);
 int wait_one(rsasa_context *ctx, Pending &pd);
 int wait_oldest(rsasa_context *ctx);
 int wait_pending(rsasa_context *ctx);
 int resolve_ctx(rsasa_context *&ctx);
 int context_create(int device, int own_queues, rsasa_context_t **out_ctx);  // own_queues: rsasa_context::own_queues
-void neighbors_release(rsasa_context *ctx);  // frees the neighbour calls' workspace (rsasa_context_destroy)
 int batch_enqueue(rsasa_context *ctx, const rsasa_device_batch_t *batch, float probe_radius, size_t n_points, void *hip_stream,
                   bool ids_needed_known);  // rsasa_batch_enqueue with the host's verdict on the ids
 

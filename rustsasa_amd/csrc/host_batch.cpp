@@ -135,30 +135,15 @@ int small_reserve(rsasa_context *ctx, const SmallLayout &l, const Lattice &lat, 
 {
     int rc;
     const size_t host_bytes = l.in_bytes + l.out_bytes;
-    if (own_staging && host_bytes > ctx->h_small_cap) {
-        if (ctx->h_small) {
-            RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            RS_HIP(ctx, hipHostFree(ctx->h_small));
-            ctx->h_small = nullptr;
-            ctx->h_small_cap = 0;
-        }
-        RS_HIP(ctx, hipHostMalloc(&ctx->h_small, host_bytes * 2, hipHostMallocDefault));
-        ctx->h_small_cap = host_bytes * 2;
+    if (own_staging && host_bytes > ctx->h_small.cap) {
+        if (ctx->h_small.p) RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RS_HIP(ctx, ctx->h_small.regrow(host_bytes * 2));
     }
-    const size_t N = l.N;
     if ((rc = reserve(ctx, ctx->small_in, l.in_bytes))) return rc;
     if (own_staging && (rc = reserve(ctx, ctx->small_out, l.out_bytes))) return rc;
-    if ((rc = reserve(ctx, ctx->sid_sorted, N * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->deferred_list, N * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->claim, kClaimBytes))) return rc;
-    if ((rc = reserve(ctx, ctx->rank_of, N * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->cells, (size_t)(l.tail_begin + 8) * 4))) return rc;
-    if ((rc = reserve(ctx, ctx->sorted_xyzr, N * 16))) return rc;
-    if ((rc = reserve(ctx, ctx->sorted_orig, N * 4))) return rc;
-    const bool keep_ids = l.has_id && !occlusion_uses_mx(ctx->tuning, lat, (uint32_t)N);
-    if (keep_ids && (rc = reserve(ctx, ctx->sorted_id, N * 8))) return rc;
-    if (l.has_id && (rc = reserve(ctx, ctx->sorted_id32, N * 4))) return rc;
-    return RSASA_OK;
+    // (grids, windows and status are in the staging block; the cell array holds the batch's LDS windows)
+    if ((rc = ctx->ws[0].reserve_sorted(ctx, l.N, (size_t)(l.tail_begin + 8), l.has_id))) return rc;
+    return ctx->ws[0].reserve_occlusion(ctx, lat, l.N, l.has_id, false, false);
 }
 
 // Runs the staged batch: ONE upload (inputs + grids + status), four launches (LDS binning, the two occlusion kernels,
@@ -192,7 +177,6 @@ int small_run(rsasa_context *ctx, const SmallLayout &l, const Lattice &lat, cons
                             l.has_id ? (uint64_t *)(d + l.o_id) : nullptr, h, d, (uint32_t)l.o_x, st);
     else if (!single) RS_HIP(ctx, hipMemcpyAsync(d, h, l.in_bytes, hipMemcpyHostToDevice, st));
     const char *src = single ? h : d;
-    const bool keep_ids = l.has_id && !occlusion_uses_mx(ctx->tuning, lat, (uint32_t)N);
 
     BatchView v{};
     v.x = (const float *)(src + l.o_x); v.y = (const float *)(src + l.o_y); v.z = (const float *)(src + l.o_z);
@@ -203,19 +187,11 @@ int small_run(rsasa_context *ctx, const SmallLayout &l, const Lattice &lat, cons
     v.probe = l.probe;
     v.grids = (StructGrid *)(d + l.o_grid);
     v.status = (BatchStatus *)d;
-    v.sid_sorted = (uint32_t *)ctx->sid_sorted.p;
-    v.deferred_list = (uint32_t *)ctx->deferred_list.p;
-    v.claim = (uint32_t *)ctx->claim.p;
-    v.cell_of = (uint32_t *)ctx->cell_of.p;
-    v.rank_of = (uint32_t *)ctx->rank_of.p;
-    v.cells = (uint32_t *)ctx->cells.p;
+    ctx->ws[0].sorted_view(v);
+    ctx->ws[0].occlusion_view(v);
     v.cell_capacity = l.tail_begin + 8;
     v.windows = (uint4 *)(d + l.o_win);
     v.window_capacity = (uint32_t)W;
-    v.sorted_xyzr = (float4 *)ctx->sorted_xyzr.p;
-    v.sorted_orig = (uint32_t *)ctx->sorted_orig.p;
-    v.sorted_id = keep_ids ? (uint64_t *)ctx->sorted_id.p : nullptr;
-    v.sorted_id32 = l.has_id ? (uint32_t *)ctx->sorted_id32.p : nullptr;
     // (the single-structure call also gets its results written straight into the pinned block)
     char *outp = single || zero_copy ? hout : dout;
     v.atom_sasa = (float *)(outp + l.o_oa);
@@ -296,7 +272,7 @@ int run_small_host_batch(rsasa_context *ctx, const SmallSource &in, const uint32
     SmallLayout lay = small_layout(S, N, W, R, in.has_id(), total_cells);
     lay.probe = probe;
     if ((rc = small_reserve(ctx, lay, lat, true))) return rc;
-    char *h = (char *)ctx->h_small;
+    char *h = (char *)ctx->h_small.p;
     small_fill(in, 0, (uint32_t)N, lay, h, 0);
     if (R) std::memcpy(h + lay.o_res, ro, (R + 1) * 4);
     char *hout = h + lay.in_bytes;
@@ -352,8 +328,8 @@ struct H2HTrace {
             r.host_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - epoch()).count();
         }
         for (auto &row : ctx->tr_ev)
-            for (hipEvent_t &e : row)
-                if (!e) (void)hipEventCreate(&e);
+            for (Event &e : row)
+                if (!e.h) (void)hipEventCreate(&e.h);
     }
     void rec(int k, int i, hipStream_t s) const
     {
@@ -538,7 +514,7 @@ struct HostBatch {
     {
         int rc;
         bx[0] = &ctx->in_x; by[0] = &ctx->in_y; bz[0] = &ctx->in_z; br[0] = &ctx->in_r;
-        bi[0] = &ctx->in_id; bo[0] = &ctx->in_res; oa[0] = &ctx->atom_sasa; orr[0] = &ctx->out_res;
+        bi[0] = &ctx->in_id; bo[0] = &ctx->in_res; oa[0] = &ctx->ws[0].atom_sasa; orr[0] = &ctx->out_res;
         for (int k = 1; k < kSlots; k++) {
             rsasa_context::MoreSlot &m = ctx->more[k - 1];
             bx[k] = &m.x; by[k] = &m.y; bz[k] = &m.z; br[k] = &m.r; bi[k] = &m.id; bo[k] = &m.res; oa[k] = &m.atom_sasa; orr[k] = &m.out_res;
@@ -600,16 +576,9 @@ struct HostBatch {
             }
             for (int k = 0; k < n_slots; k++)
                 if ((rc = reserve(ctx, ctx->in_pack[k], largest))) return rc;
-            if (total > ctx->h_pack_cap) {
-                if (ctx->h_pack) {
-                    RS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
-                    RS_HIP(ctx, hipHostFree(ctx->h_pack));
-                    ctx->h_pack = nullptr;
-                    ctx->h_pack_cap = 0;
-                }
-                const size_t cap = total + total / 4;
-                RS_HIP(ctx, hipHostMalloc((void **)&ctx->h_pack, cap, hipHostMallocDefault));
-                ctx->h_pack_cap = cap;
+            if (total > ctx->h_pack.cap) {
+                if (ctx->h_pack.p) RS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
+                RS_HIP(ctx, ctx->h_pack.regrow(total + total / 4));
             }
         }
         // Ids that are all different within their structure change nothing (BatchView::ids_check).  The pipelined path's
@@ -628,17 +597,12 @@ struct HostBatch {
         fold_job.assign(cut.size(), 0);
         for (int k = 0; k < n_slots && want_res && !piped; k++) {
             rsasa_context::HostSlot &hs = ctx->slot[k];
-            if (max_res + 1 <= hs.h_res_cap) continue;
-            if (hs.h_res) {
+            if ((max_res + 1) * sizeof(uint32_t) <= hs.h_res.cap) continue;
+            if (hs.h_res.p) {
                 RS_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
                 RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                RS_HIP(ctx, hipHostFree(hs.h_res));
-                hs.h_res = nullptr;
-                hs.h_res_cap = 0;
             }
-            const size_t cap = max_res + 1 + max_res / 4;
-            RS_HIP(ctx, hipHostMalloc((void **)&hs.h_res, cap * sizeof(uint32_t), hipHostMallocDefault));
-            hs.h_res_cap = cap;
+            RS_HIP(ctx, hs.h_res.regrow((max_res + 1 + max_res / 4) * sizeof(uint32_t)));
         }
         for (int k = 0; k < n_slots && piped && id && !fold_ids; k++)
             if ((rc = reserve(ctx, *bi[k], max_atoms * 8))) return rc;
@@ -655,15 +619,9 @@ struct HostBatch {
         stage_atoms = (out_atom_sasa && !atoms_direct) ? max_atoms * 4 : 0;
         stage_bytes = stage_atoms + ((want_res && !res_direct) ? max_res * 4 : 0);
         for (int k = 0; k < n_slots && stage_bytes; k++) {
-            if (stage_bytes <= ctx->h_out_cap[k]) continue;
-            if (ctx->h_out[k]) {
-                RS_HIP(ctx, hipStreamSynchronize(ctx->d2h_stream));
-                RS_HIP(ctx, hipHostFree(ctx->h_out[k]));
-                ctx->h_out[k] = nullptr;
-                ctx->h_out_cap[k] = 0;
-            }
-            RS_HIP(ctx, hipHostMalloc(&ctx->h_out[k], stage_bytes + stage_bytes / 4, hipHostMallocDefault));
-            ctx->h_out_cap[k] = stage_bytes + stage_bytes / 4;
+            if (stage_bytes <= ctx->h_out[k].cap) continue;
+            if (ctx->h_out[k].p) RS_HIP(ctx, hipStreamSynchronize(ctx->d2h_stream));
+            RS_HIP(ctx, ctx->h_out[k].regrow(stage_bytes + stage_bytes / 4));
         }
         return RSASA_OK;
     }
@@ -698,7 +656,7 @@ struct HostBatch {
         }
         if (piped) {
             // the sub-batch's pinned block (the workers have filled in ids and radius codes): table and offsets, one copy
-            char *blk = ctx->h_pack + pack[c].base;
+            char *blk = (char *)ctx->h_pack.p + pack[c].base;
             if (use_codes[c]) std::memcpy(blk, ctx->radius_codec.table, kTableWords * 4);
             if (want_res) {
                 const size_t r0 = res_cut[c], r1 = res_cut[c + 1];
@@ -708,7 +666,7 @@ struct HostBatch {
             RS_HIP(ctx, hipMemcpyAsync(ctx->in_pack[k].p, blk, drop_ids[c] ? pack[c].o_id : pack[c].bytes, hipMemcpyHostToDevice, st));
         } else if (want_res) {
             const size_t r0 = res_cut[c], r1 = res_cut[c + 1];
-            uint32_t *ro = ctx->slot[k].h_res;
+            uint32_t *ro = (uint32_t *)ctx->slot[k].h_res.p;
             for (size_t i = r0; i <= r1; i++) ro[i - r0] = residue_offsets[i] - (uint32_t)a0;
             RS_HIP(ctx, hipMemcpyAsync(bo[k]->p, ro, (r1 - r0 + 1) * 4, hipMemcpyHostToDevice, st));
         }
@@ -719,7 +677,7 @@ struct HostBatch {
     {
         if (!staged[k].active) return RSASA_OK;
         RS_HIP(ctx, hipEventSynchronize(ctx->ev_d2h[k]));
-        const char *h = (const char *)ctx->h_out[k];
+        const char *h = (const char *)ctx->h_out[k].p;
         if (out_atom_sasa && !atoms_direct && staged[k].na)
             std::memcpy(out_atom_sasa + staged[k].a0, h, staged[k].na * 4);
         if (want_res && !res_direct && staged[k].nr)
@@ -734,7 +692,7 @@ struct HostBatch {
         const int k = (int)(c % kSlots);
         const size_t a0 = structure_offsets[cut[c]], na = atoms_of(c);
         const size_t r0 = res_cut[c], nr = residues_of(c);
-        char *h = (char *)ctx->h_out[k];
+        char *h = (char *)ctx->h_out[k].p;
         if (out_atom_sasa && na)
             RS_HIP(ctx, hipMemcpyAsync(atoms_direct ? (void *)(out_atom_sasa + a0) : (void *)h, oa[k]->p, na * 4,
                                        hipMemcpyDeviceToHost, dn));
@@ -806,11 +764,8 @@ struct HostBatch {
 
     void check(int k, Attempt &at)  // status of the sub-batch that used host slot k (its event has been waited for)
     {
-        const BatchStatus stt = *ctx->slot[k].h_status;
-        if (stt.grid_too_large && !at.err)
-            at.err = fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "a structure's cell grid exceeds 2^31 cells (coordinates too sparse)");
-        if (stt.bad_input && !at.err)
-            at.err = fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "probe_radius + max radius must be a positive finite number");
+        const BatchStatus stt = ctx->slot[k].status();
+        if (!at.err) at.err = grid_input_error(ctx, stt);
         if (stt.overflow) at.need_cells = std::max<uint64_t>(at.need_cells, stt.total_cells);
         else ctx->tuning.deferred_hint = stt.deferred;
         if (!stt.overflow && ctx->slot[k].ids_check) {
@@ -829,7 +784,7 @@ struct HostBatch {
         if (code_radii) ctx->radius_codec.reset();
         for (size_t c = 0; c < n_sub; c++) {
             const size_t a0 = structure_offsets[cut[c]], na = atoms_of(c);
-            char *blk = ctx->h_pack + pack[c].base;
+            char *blk = (char *)ctx->h_pack.p + pack[c].base;
             IdOrder order;
             ids_matter[c].store(0);
             if (fold_ids && check_ids) {
@@ -933,7 +888,7 @@ struct HostBatch {
                 return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
         if (structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must span [0, n_atoms]");
         hipStream_t cp = ctx->copy_stream;
-        if (!ctx->stream2) RS_HIP(ctx, new_stream(ctx, &ctx->stream2, 2));
+        if (!ctx->stream2) RS_HIP(ctx, new_stream(ctx, &ctx->stream2.h, 2));
         for (int attempt = 0;; attempt++) {
             Attempt at;
             LinkHold turn;  // (released without an event on an error return)
@@ -956,9 +911,7 @@ struct HostBatch {
             tr.device_side(n_sub);
             if (at.err) return at.err;
             if (!at.need_cells) return RSASA_OK;
-            if (at.need_cells >= 0xFFFFFFF0ull || attempt >= 3)
-                return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "batch needs more than 2^32 grid cells; split it");
-            ctx->cell_capacity = at.need_cells + at.need_cells / 8 + 1024;
+            if ((rc = grid_grow(ctx, at.need_cells, attempt, ctx->cell_capacity)) != kGridAgain) return rc;
         }
     }
 };
@@ -1146,7 +1099,7 @@ static int host_batch_wait(rsasa_context_t *ctx, bool *took)
         for (auto it = hs->jobs.begin(); it != hs->jobs.end(); ++it)
             if (*it == job) { hs->jobs.erase(it); break; }
     }
-    hs->cv_done.notify_all();  // (an enqueue may be waiting for room)
+    hs->cv_done.notify_all();
     if (job->rc) return fail(ctx, job->rc, job->error.c_str());
     return RSASA_OK;
 }
@@ -1291,7 +1244,7 @@ int rsasa_calculate_sasa_trajectory(rsasa_context_t *ctx, const float *xyz, size
         if ((rc = reserve(ctx, ctx->in_z, N * 4))) return rc;
         if ((rc = reserve(ctx, ctx->in_r, N * 4))) return rc;
         if (id && (rc = reserve(ctx, ctx->in_id, N * 8))) return rc;
-        if ((rc = reserve(ctx, ctx->atom_sasa, N * 4))) return rc;
+        if ((rc = reserve(ctx, ctx->ws[0].atom_sasa, N * 4))) return rc;
         if (want_res) {
             if ((rc = reserve(ctx, ctx->in_res, (R + 1) * 4))) return rc;
             if ((rc = reserve(ctx, ctx->out_res, R * 4))) return rc;
@@ -1315,12 +1268,12 @@ int rsasa_calculate_sasa_trajectory(rsasa_context_t *ctx, const float *xyz, size
         bt.n_atoms = N;
         bt.residue_offsets = want_res ? (const uint32_t *)ctx->in_res.p : nullptr;
         bt.n_residues = R;
-        bt.out_atom_sasa = (float *)ctx->atom_sasa.p;
+        bt.out_atom_sasa = (float *)ctx->ws[0].atom_sasa.p;
         bt.out_residue_sasa = want_res ? (float *)ctx->out_res.p : nullptr;
         if ((rc = rsasa_batch_enqueue(ctx, &bt, probe_radius, n_points, nullptr))) return rc;
         if ((rc = rsasa_batch_wait(ctx))) return rc;
         if (out_atom_sasa)
-            RS_HIP(ctx, hipMemcpy(out_atom_sasa + f0 * n_atoms, ctx->atom_sasa.p, N * 4, hipMemcpyDeviceToHost));
+            RS_HIP(ctx, hipMemcpy(out_atom_sasa + f0 * n_atoms, ctx->ws[0].atom_sasa.p, N * 4, hipMemcpyDeviceToHost));
         if (want_res && res_exact)
             RS_HIP(ctx, hipMemcpy(out_residue_sasa + f0 * n_residues, ctx->out_res.p, R * 4,
                                   hipMemcpyDeviceToHost));

@@ -28,17 +28,13 @@ int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     rsasa_context::Workspace &W = ctx->nb_ws;
     hipStream_t st = ctx->stream;
 
-    std::vector<Segment> segs;
-    bool has_tail = false;
-    for (size_t s = 0; s < S; s++) {
-        const uint32_t b = so[s], e = so[s + 1];
-        has_tail |= e - b >= kLdsMaxAtoms;
-        for (uint32_t a = b; a < e; a += kSegmentAtoms)
-            segs.push_back(Segment{(uint32_t)s, a, std::min(e, a + kSegmentAtoms), a != b ? 1u : 0u});
-    }
+    const SegmentCount sc = count_segments(so, S);
+    std::vector<Segment> segs(sc.n_seg);
+    write_segments(so, S, segs.data(), nullptr);
+    const bool has_tail = sc.has_tail;
     const bool has_id = id != nullptr;
-    if (!ctx->nb_host) RS_HIP(ctx, hipHostMalloc(&ctx->nb_host, sizeof(NbHost), hipHostMallocDefault));
-    NbHost *h = static_cast<NbHost *>(ctx->nb_host);
+    if (!ctx->nb_host.p) RS_HIP(ctx, ctx->nb_host.regrow(sizeof(NbHost)));
+    NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
 
     if ((rc = reserve(ctx, ctx->nb_x, N * 4)) || (rc = reserve(ctx, ctx->nb_y, N * 4)) || (rc = reserve(ctx, ctx->nb_z, N * 4)) ||
         (rc = reserve(ctx, ctx->nb_r, N * 4)) || (has_id && (rc = reserve(ctx, ctx->nb_id, N * 8))) ||
@@ -51,22 +47,10 @@ int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     if (has_id) RS_HIP(ctx, hipMemcpyAsync(ctx->nb_id.p, id, N * 8, hipMemcpyHostToDevice, st));
     if (idx_map) RS_HIP(ctx, hipMemcpyAsync(ctx->nb_map.p, idx_map, N * 4, hipMemcpyHostToDevice, st));
 
-    // ---- the grid (as enqueue_batch builds it, without the id check: every id takes part), grown until the cells fit
-    if (ctx->nb_cell_capacity == 0) ctx->nb_cell_capacity = std::max<uint64_t>(1u << 16, 20ull * N + 512ull * S);
+    // ---- the grid (without the id check: every id takes part), grown until the cells fit
     BatchView v{};
     for (int attempt = 0;; attempt++) {
-        ctx->nb_cell_capacity = std::min<uint64_t>(ctx->nb_cell_capacity, 0xFFFFFFF0ull);
-        const uint64_t window_capacity = std::min<uint64_t>(2 * ctx->nb_cell_capacity / kWindowCells + S + 1, 0x7FFFFFFFull);
-        if ((rc = reserve(ctx, W.segments, std::max<size_t>(segs.size(), 1) * sizeof(Segment))) ||
-            (rc = reserve(ctx, W.acc, S * sizeof(StructAcc))) || (rc = reserve(ctx, W.grids, S * sizeof(StructGrid))) ||
-            (rc = reserve(ctx, W.grid_sums, (S + 255) / 256 * 32)) || (rc = reserve(ctx, W.sid_sorted, N * 4)) ||
-            (has_tail && (rc = reserve(ctx, W.cell_of, N * 4))) || (rc = reserve(ctx, W.rank_of, N * 4)) ||
-            (rc = reserve(ctx, W.cells, (size_t)(ctx->nb_cell_capacity + 1 + 3) * 4)) ||
-            (rc = reserve(ctx, W.windows, (size_t)window_capacity * sizeof(uint4))) ||
-            (rc = reserve(ctx, W.scan_sums, kScanBlocks * 4)) || (rc = reserve(ctx, W.sorted_xyzr, N * 16)) ||
-            (rc = reserve(ctx, W.sorted_orig, N * 4)) || (has_id && (rc = reserve(ctx, W.sorted_id32, N * 4))) ||
-            (rc = reserve(ctx, W.status, sizeof(BatchStatus))))
-            return rc;
+        if ((rc = W.reserve_grid(ctx, N, S, segs.size(), ctx->nb_cell_capacity, has_tail, has_id))) return rc;
         if (!segs.empty())
             RS_HIP(ctx, hipMemcpyAsync(W.segments.p, segs.data(), segs.size() * sizeof(Segment), hipMemcpyHostToDevice, st));
         v = BatchView{};
@@ -76,37 +60,15 @@ int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
         v.n_atoms = (uint32_t)N; v.n_structures = (uint32_t)S; v.n_segments = (uint32_t)segs.size();
         v.probe = probe;
         v.max_r_override = max_r;
-        v.segments = (const Segment *)W.segments.p;
-        v.acc = (StructAcc *)W.acc.p;
-        v.grids = (StructGrid *)W.grids.p;
-        v.grid_sums = (GridSums *)W.grid_sums.p;
-        v.sid_sorted = (uint32_t *)W.sid_sorted.p;
-        v.cell_of = (uint32_t *)W.cell_of.p;
-        v.rank_of = (uint32_t *)W.rank_of.p;
-        v.cells = (uint32_t *)W.cells.p;
-        v.cell_capacity = ctx->nb_cell_capacity;
-        v.windows = (uint4 *)W.windows.p;
-        v.window_capacity = (uint32_t)window_capacity;
-        v.scan_block_sums = (uint32_t *)W.scan_sums.p;
-        v.sorted_xyzr = (float4 *)W.sorted_xyzr.p;
-        v.sorted_orig = (uint32_t *)W.sorted_orig.p;
-        v.sorted_id32 = has_id ? (uint32_t *)W.sorted_id32.p : nullptr;
-        v.status = (BatchStatus *)W.status.p;
+        W.grid_view(v);
         launch_grid_prepare(v, st);
         launch_sort_lds(v, st);
         if (has_tail) launch_sort_tail(v, st);
         RS_HIP(ctx, hipMemcpyAsync(&h->status, W.status.p, sizeof(BatchStatus), hipMemcpyDeviceToHost, st));
         RS_HIP(ctx, hipGetLastError());
         RS_HIP(ctx, hipStreamSynchronize(st));
-        const BatchStatus stt = h->status;
-        if (stt.grid_too_large)
-            return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "a structure's cell grid exceeds 2^31 cells (coordinates too sparse)");
-        if (stt.bad_input)
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "probe_radius + max radius must be a positive finite number");
-        if (!stt.overflow) break;
-        if (stt.total_cells >= 0xFFFFFFF0ull || attempt >= 3)
-            return fail(ctx, RSASA_ERR_GRID_TOO_LARGE, "batch needs more than 2^32 grid cells; split it");
-        ctx->nb_cell_capacity = stt.total_cells + stt.total_cells / 8 + 1024;  // (as wait_one: grow, run again)
+        if ((rc = grid_verdict(ctx, h->status, attempt, ctx->nb_cell_capacity)) == RSASA_OK) break;
+        if (rc != kGridAgain) return rc;
     }
 
     // ---- counts, offsets
@@ -152,23 +114,6 @@ int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
 }
 
 }  // namespace
-
-namespace rsasa {
-
-void neighbors_release(rsasa_context *ctx)
-{
-    rsasa_context::Workspace &W = ctx->nb_ws;
-    for (DeviceBuffer *b : {&W.segments, &W.acc, &W.grids, &W.grid_sums, &W.sid_sorted, &W.deferred_list, &W.cell_of, &W.rank_of,
-                            &W.cells, &W.windows, &W.scan_sums, &W.sorted_xyzr, &W.sorted_orig, &W.sorted_id, &W.sorted_id32,
-                            &W.status, &W.atom_sasa, &W.claim, &W.ids_seg, &ctx->nb_x, &ctx->nb_y, &ctx->nb_z, &ctx->nb_r,
-                            &ctx->nb_id, &ctx->nb_map, &ctx->nb_counts, &ctx->nb_offsets, &ctx->nb_parts, &ctx->nb_info,
-                            &ctx->nb_entries, &ctx->nb_spill, &ctx->nb_recs})
-        release(*b);
-    if (ctx->nb_host) (void)hipHostFree(ctx->nb_host);
-    ctx->nb_host = nullptr;
-}
-
-}  // namespace rsasa
 
 extern "C" {
 
