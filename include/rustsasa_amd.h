@@ -36,7 +36,8 @@ extern "C" {
  *    queued returns RSASA_ERR_QUEUE_FULL at once (it used to wait for the oldest batch and then fail);
  * nothing else changed, nothing removed.
  * Additive under 4 (callers detect them by symbol): rsasa_neighbor_t, rsasa_precompute_neighbors,
- * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL. */
+ * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL; rsasa_accessible_points,
+ * rsasa_accessible_points_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -346,6 +347,67 @@ int rsasa_precompute_neighbors_batch(rsasa_context_t *ctx,
                                      float probe_radius, float max_radius,
                                      uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
                                      size_t entries_capacity);
+
+/* ---- accessible points -------------------------------------------------- */
+
+/* WHICH sphere points of each atom are accessible: the decisions the SASA
+ * value of an atom counts (AtomSasaKernel, reference src/lib.rs:96-223), one
+ * bit per point - SAS dot surfaces, surface point clouds, directional
+ * exposure, point-by-point checks of a value.
+ *
+ * Layout: words = (n_points + 31) / 32; atom i owns
+ * out_masks[i * words .. (i + 1) * words).  Bit (p & 31) of word (p >> 5) is 1
+ * exactly when lattice point p - in the order of rsasa_sphere_points
+ * (lib.rs:43-66) - is accessible; the bits past n_points in the last word
+ * are 0.
+ *
+ * Bit p is the reference's own decision for that point.  The candidates are
+ * those of calculate_sasa_internal: the lists of rsasa_precompute_neighbors
+ * with max_radius = fold(0, max) of the structure's radii (NaN radii skipped,
+ * lib.rs:259-262), ids as there.  With v = centre - neighbour,
+ * d^2 = vx*vx + vy*vy + vz*vz, R = radius + probe and
+ * limit = (threshold_squared - d^2 - R*R) / (2 R) (the IEEE quotient,
+ * lib.rs:129-136), a point p < n_points - n_points % W is occluded when some
+ * entry gives fmaf(sx, vx, fmaf(sy, vy, sz*vz)) < limit (lib.rs:143-146), any
+ * later point when some entry gives (sx*vx + sy*vy) + sz*vz <= limit
+ * (lib.rs:185-186,206-207); W is the context's lane count
+ * (rsasa_context_set_simd_width).  Both rules are ORs over the list, so the
+ * list's order does not matter.  popcount of an atom's words is therefore the
+ * reference's accessible-point count k, and out_sasa[i] (nullable) is
+ * ((12.566371f * R*R) * (float)k) * (1.0f / (float)n_points) (lib.rs:220-222):
+ * bit for bit the value of rsasa_calculate_sasa_batch on the same input.
+ *
+ * The "Non-finite input" paragraph above holds: an atom with a NaN coordinate
+ * or a NaN radius has a mask of all ones (its out_sasa is NaN for a NaN
+ * radius); an infinite coordinate returns RSASA_ERR_GRID_TOO_LARGE and the
+ * context stays usable.  n_points == 0, probe_radius + largest radius not a
+ * positive finite number, or structure_offsets that are not non-decreasing
+ * from 0 return RSASA_ERR_INVALID_ARGUMENT.
+ *
+ * Like the neighbour calls, both are synchronous and run on the GPU in the
+ * neighbour calls' workspace on the context's first stream: device batches in
+ * flight (rsasa_batch_enqueue) are neither waited for nor disturbed.  Only the
+ * masks (n_points / 8 bytes per atom, rounded up to whole words) and the
+ * values cross the link; the lists stay on the device. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).
+ * out_masks: [n_atoms * words]; out_sasa: [n_atoms] or NULL. */
+int rsasa_accessible_points(rsasa_context_t *ctx,
+                            const float *x, const float *y, const float *z, const float *radius,
+                            const uint64_t *id, size_t n_atoms,
+                            float probe_radius, size_t n_points,
+                            uint32_t *out_masks, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each).
+ * out_masks: [structure_offsets[n_structures] * words]; out_atom_sasa:
+ * [structure_offsets[n_structures]] or NULL. */
+int rsasa_accessible_points_batch(rsasa_context_t *ctx,
+                                  const float *x, const float *y, const float *z, const float *radius,
+                                  const uint64_t *id,
+                                  const uint32_t *structure_offsets, size_t n_structures,
+                                  float probe_radius, size_t n_points,
+                                  uint32_t *out_masks, float *out_atom_sasa);
 
 /* ---- measurement ------------------------------------------------------- */
 

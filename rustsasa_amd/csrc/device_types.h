@@ -202,6 +202,18 @@ struct NbArgs {
     NbSpillRec *spill_recs;
 };
 
+// ---- accessible points (points.hip, rsasa_accessible_points*) ----
+// The lists of a finished neighbour run (NbArgs: offsets, out) tested against the lattice, bits out.
+struct PtArgs {
+    BatchView b;                        // the binned batch of the neighbour run (input columns, grids, sorted order)
+    const unsigned long long *offsets;  // [n_atoms + 1] NbArgs::offsets
+    const uint2 *entries;               // NbArgs::out: (threshold_squared bits, idx within the structure)
+    const float *lx, *ly, *lz;          // the lattice in the reference's order (lib.rs:43-66), zero padded to whole 64s
+    uint32_t n_points, n_fused, words;  // words = (n_points + 31) / 32 per atom
+    uint32_t *masks;                    // [n_atoms][words], input order: bit p & 31 of word p >> 5 = point p exposed
+    float *sasa;                        // [n_atoms] or null: ((4 pi R^2) popcount) / n_points (lib.rs:220-222)
+};
+
 // Grid and status of a one-structure batch, computed by the host and handed to k_sort_window<true> as
 // kernel arguments.
 struct SingleJob {
@@ -260,6 +272,8 @@ void launch_residue_sums(const BatchView &b, hipStream_t stream);
 // Neighbour lists (neighbors.hip) on a binned batch: counts, offsets and NbInfo; then the entries.
 void launch_neighbor_count(const NbArgs &a, hipStream_t stream);
 void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
+// The point masks (points.hip) from those lists.
+void launch_accessible_points(const PtArgs &a, hipStream_t stream);
 // Pinned 24-byte atom records (x, y, z, r, id) -> device columns, and `hdr_bytes` of header beside them (combine.cpp).
 void launch_unpack_atoms(const void *records, uint32_t n_atoms, float *x, float *y, float *z, float *r, uint64_t *id,
                          const void *hdr_src, void *hdr_dst, uint32_t hdr_bytes, hipStream_t stream);

@@ -450,6 +450,10 @@ struct rsasa_context {
     DeviceBuffer nb_x, nb_y, nb_z, nb_r, nb_id, nb_map, nb_counts, nb_offsets, nb_parts, nb_info, nb_entries, nb_spill, nb_recs;
     PinnedBlock nb_host;           // the BatchStatus and NbInfo of the last neighbour call
     uint64_t nb_cell_capacity = 0;
+    // rsasa_accessible_points*: the masks and values of the last call, and the lattice in the reference's order (the SASA
+    // path's cached lattices reorder the points above 128)
+    DeviceBuffer pt_masks, pt_sasa, pt_lattice;
+    size_t pt_lattice_points = 0;  // the point count pt_lattice holds (0: none)
 };
 
 namespace rsasa {

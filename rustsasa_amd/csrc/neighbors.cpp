@@ -1,6 +1,7 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h): the
 // batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws), then
-// neighbors.hip counts, scans and fills the lists.  Host code only.
+// neighbors.hip counts, scans and fills the lists.  The accessible-point entry points (rsasa_accessible_points /
+// _batch) run the same stages and hand the lists, still on the device, to points.hip.  Host code only.
 #include "engine_internal.h"
 
 namespace {
@@ -10,21 +11,18 @@ using namespace rsasa;
 struct NbHost {  // the pinned block the device's verdicts come back in
     BatchStatus status;
     NbInfo info;
+    uint64_t last_offset;  // offsets[N], when the caller wants no host copy of the offsets
 };
 
-// One run over columns already in host memory: S structures, N atoms.  idx_map (host, nullable): input atom -> the
-// index written to the entries.
-int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
-           const uint32_t *so, size_t S, size_t N, const uint32_t *idx_map, float probe, float max_r,
-           uint64_t *out_offsets, rsasa_neighbor_t *out_entries, size_t cap)
+// The upload, the grid and the counts of a run over columns already in host memory: S structures, N >= 1 atoms.
+// idx_map (host, nullable): input atom -> the index written to the entries.  out_offsets (nullable): [N + 1], the
+// offsets are copied there.  On RSASA_OK `a` describes the device lists (everything but their entries) and `info` their
+// sizes.  The caller holds the context's mutex and has made its device current.
+int nb_count(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+             const uint32_t *so, size_t S, size_t N, const uint32_t *idx_map, float probe, float max_r,
+             uint64_t *out_offsets, NbArgs &a, NbInfo &info)
 {
-    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    RS_DEVICE(ctx);
     int rc;
-    if (N == 0) {
-        out_offsets[0] = 0;
-        return RSASA_OK;
-    }
     rsasa_context::Workspace &W = ctx->nb_ws;
     hipStream_t st = ctx->stream;
 
@@ -72,7 +70,7 @@ int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     }
 
     // ---- counts, offsets
-    NbArgs a{};
+    a = NbArgs{};
     a.b = v;
     if ((rc = reserve(ctx, ctx->nb_counts, N * 4)) || (rc = reserve(ctx, ctx->nb_offsets, (N + 1) * 8)) ||
         (rc = reserve(ctx, ctx->nb_parts, 4 * 1024 * 8)) || (rc = reserve(ctx, ctx->nb_info, sizeof(NbInfo))))
@@ -85,16 +83,22 @@ int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     RS_HIP(ctx, hipMemsetAsync(a.info, 0, sizeof(NbInfo), st));
     launch_neighbor_count(a, st);
     RS_HIP(ctx, hipMemcpyAsync(&h->info, a.info, sizeof(NbInfo), hipMemcpyDeviceToHost, st));
-    RS_HIP(ctx, hipMemcpyAsync(out_offsets, a.offsets, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    if (out_offsets) RS_HIP(ctx, hipMemcpyAsync(out_offsets, a.offsets, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    else RS_HIP(ctx, hipMemcpyAsync(&h->last_offset, a.offsets + N, 8, hipMemcpyDeviceToHost, st));
     RS_HIP(ctx, hipGetLastError());
     RS_HIP(ctx, hipStreamSynchronize(st));
-    const NbInfo info = h->info;
-    if (info.total != out_offsets[N]) return fail(ctx, RSASA_ERR_INTERNAL, "neighbour offsets disagree with their total");
-    if (!out_entries || cap < info.total)
-        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_entries holds fewer entries than out_offsets[n]");
-    if (info.total == 0) return RSASA_OK;
+    info = h->info;
+    if (info.total != (out_offsets ? out_offsets[N] : h->last_offset))
+        return fail(ctx, RSASA_ERR_INTERNAL, "neighbour offsets disagree with their total");
+    return RSASA_OK;
+}
 
-    // ---- entries
+// The entries of the lists nb_count sized (info.total >= 1), sorted, in a.out on the device.
+int nb_fill(rsasa_context *ctx, NbArgs &a, const NbInfo &info)
+{
+    int rc;
+    hipStream_t st = ctx->stream;
+    NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
     if ((rc = reserve(ctx, ctx->nb_entries, info.total * 8)) ||
         (info.spill_atoms && ((rc = reserve(ctx, ctx->nb_spill, info.spill_entries * sizeof(NbKey))) ||
                               (rc = reserve(ctx, ctx->nb_recs, info.spill_atoms * sizeof(NbSpillRec))))))
@@ -108,7 +112,84 @@ int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     RS_HIP(ctx, hipStreamSynchronize(st));
     if (h->info.mismatch || h->info.spill_cursor != info.spill_entries || h->info.spill_recs != info.spill_atoms)
         return fail(ctx, RSASA_ERR_INTERNAL, "the neighbour fill pass disagrees with its count pass");
-    RS_HIP(ctx, hipMemcpyAsync(out_entries, a.out, info.total * 8, hipMemcpyDeviceToHost, st));
+    return RSASA_OK;
+}
+
+// One neighbour-list run: S structures, N atoms (see nb_count).
+int nb_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *so, size_t S, size_t N, const uint32_t *idx_map, float probe, float max_r,
+           uint64_t *out_offsets, rsasa_neighbor_t *out_entries, size_t cap)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    NbArgs a{};
+    NbInfo info{};
+    if ((rc = nb_count(ctx, x, y, z, r, id, so, S, N, idx_map, probe, max_r, out_offsets, a, info))) return rc;
+    if (!out_entries || cap < info.total)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_entries holds fewer entries than out_offsets[n]");
+    if (info.total == 0) return RSASA_OK;
+    if ((rc = nb_fill(ctx, a, info))) return rc;
+    RS_HIP(ctx, hipMemcpyAsync(out_entries, a.out, info.total * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RSASA_OK;
+}
+
+// ---- accessible points (rsasa_accessible_points*) ----
+
+// The lattice in the reference's order (lib.rs:43-66) on the device: x | y | z, each zero padded to whole 64s.
+int pt_lattice(rsasa_context *ctx, size_t n_points, size_t &padded)
+{
+    padded = (n_points + 63) / 64 * 64;
+    if (ctx->pt_lattice_points == n_points) return RSASA_OK;
+    int rc;
+    ctx->pt_lattice_points = 0;
+    if ((rc = reserve(ctx, ctx->pt_lattice, 3 * padded * sizeof(float)))) return rc;
+    std::vector<float> h(3 * padded, 0.0f);
+    generate_sphere_points(n_points, h.data(), h.data() + padded, h.data() + 2 * padded);
+    RS_HIP(ctx, hipMemcpyAsync(ctx->pt_lattice.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->pt_lattice_points = n_points;
+    return RSASA_OK;
+}
+
+// One run of the point tests: the lists of nb_count / nb_fill with max_r = NaN - the lists calculate_sasa_internal
+// builds (lib.rs:259-267) - stay on the device and k_accessible_points turns them into masks.
+int pt_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *so, size_t S, size_t N, float probe, size_t n_points, uint32_t *out_masks, float *out_sasa)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) return RSASA_OK;
+    const size_t words = (n_points + 31) / 32;
+    size_t padded = 0;
+    if ((rc = pt_lattice(ctx, n_points, padded))) return rc;
+    NbArgs a{};
+    NbInfo info{};
+    if ((rc = nb_count(ctx, x, y, z, r, id, so, S, N, nullptr, probe, __builtin_nanf(""), nullptr, a, info))) return rc;
+    if (info.total && (rc = nb_fill(ctx, a, info))) return rc;
+    if ((rc = reserve(ctx, ctx->pt_masks, N * words * 4)) || (out_sasa && (rc = reserve(ctx, ctx->pt_sasa, N * 4)))) return rc;
+    PtArgs pa{};
+    pa.b = a.b;
+    pa.offsets = a.offsets;
+    pa.entries = (const uint2 *)ctx->nb_entries.p;  // (not read when every list is empty)
+    const float *lat = (const float *)ctx->pt_lattice.p;
+    pa.lx = lat; pa.ly = lat + padded; pa.lz = lat + 2 * padded;
+    pa.n_points = (uint32_t)n_points;
+    pa.n_fused = (uint32_t)(n_points - n_points % (size_t)ctx->simd_width);
+    pa.words = (uint32_t)words;
+    pa.masks = (uint32_t *)ctx->pt_masks.p;
+    pa.sasa = out_sasa ? (float *)ctx->pt_sasa.p : nullptr;
+    hipStream_t st = ctx->stream;
+    launch_accessible_points(pa, st);
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, hipMemcpyAsync(out_masks, pa.masks, N * words * 4, hipMemcpyDeviceToHost, st));
+    if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, pa.sasa, N * 4, hipMemcpyDeviceToHost, st));
     RS_HIP(ctx, hipStreamSynchronize(st));
     return RSASA_OK;
 }
@@ -168,6 +249,38 @@ int rsasa_precompute_neighbors_batch(rsasa_context_t *ctx, const float *x, const
     if (N && (!x || !y || !z || !radius)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
     return nb_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, nullptr, probe_radius, max_radius, out_offsets,
                   out_entries, entries_capacity);
+}
+
+int rsasa_accessible_points(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                            const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, uint32_t *out_masks,
+                            float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (n_atoms && (!x || !y || !z || !radius || !out_masks)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
+    if (n_atoms >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    const uint32_t so[2] = {0u, (uint32_t)n_atoms};
+    return pt_run(ctx, x, y, z, radius, id, so, 1, n_atoms, probe_radius, n_points, out_masks, out_sasa);
+}
+
+int rsasa_accessible_points_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                                  const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures,
+                                  float probe_radius, size_t n_points, uint32_t *out_masks, float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!structure_offsets) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
+    if (n_structures >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "too many structures");
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1])
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (n_structures && structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets[0] must be 0");
+    if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    if (N && (!x || !y || !z || !radius || !out_masks)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    return pt_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_masks, out_atom_sasa);
 }
 
 }  // extern "C"

@@ -1,0 +1,169 @@
+// Accessible-point kernel (rsasa_accessible_points*, gfx950 only): which sphere points of each atom the reference finds
+// exposed (AtomSasaKernel::with_simd, reference src/lib.rs:96-223), as bit masks, from the neighbour lists that
+// neighbors.hip built in HBM (k_neighbor_count / k_nb_scan_* / k_neighbor_fill with max_r = NaN: the SASA path's lists).
+//
+//   k_accessible_points   one wave per cell-sorted atom; lanes over 64-point chunks of the lattice (reference order,
+//                         zero padded), NCH chunks per pass; the atom's list is staged in LDS as (vx, vy, vz, limit),
+//                         kPtStage entries at a time, and every lane tests its points against each staged entry.  A
+//                         pass stops once its ballot of still-exposed lanes is empty.  Each chunk's exposed ballot is
+//                         two 32-bit words of the mask.
+//
+// Points [0, n_fused) take the fused rule - mul_add(sx, vx, mul_add(sy, vy, sz * vz)) < limit (lib.rs:143-146) -, the
+// rest the remainder rule - plain products, `<=` (lib.rs:185-186,206-207).  Both rules are ORs over the list, so the
+// list's order (and the reference's early exits and cached neighbour) do not change a bit.
+// Compiled with -ffp-contract=off: d^2 and the remainder dot product are not fused, as in the reference.
+#include "device_utils.h"
+
+namespace rsasa {
+namespace {
+
+constexpr uint32_t kPtStage = 256;  // list entries a wave holds in LDS (4 KiB; lists are ~44 long at probe 1.4)
+
+// Entries [s0, s0 + n) of the atom's list -> s_ent as (vx, vy, vz, limit) (lib.rs:129-136), lanes in parallel, then
+// up to 3 entries (0, 0, 0, -inf) up to a multiple of 4: no point of the lattice is occluded by one (dot = 0, 0 < -inf
+// and 0 <= -inf are false), so the test loop reads whole groups of four.
+__device__ __forceinline__ void pt_stage(const PtArgs &a, const uint2 *ent, uint32_t s0, uint32_t n, uint32_t base,
+                                         const float4 me, float R2, float twoR, float4 *s_ent)
+{
+    const BatchView &b = a.b;
+    const uint32_t n4 = (n + 3u) & ~3u;
+    for (uint32_t e = lane_id(); e < n4; e += kWave) {
+        float4 v = make_float4(0.0f, 0.0f, 0.0f, -__builtin_inff());
+        if (e < n) {
+            const uint2 en = ent[s0 + e];
+            const uint32_t j = base + en.y;                               // idx is the index within the structure
+            const float vx = me.x - b.x[j], vy = me.y - b.y[j], vz = me.z - b.z[j];  // lib.rs:129-131
+            const float d2 = vx * vx + vy * vy + vz * vz;                 // lib.rs:132
+            const float t = __uint_as_float(en.x);                        // threshold_squared, spatial_grid.rs:336-339
+            v = make_float4(vx, vy, vz, (t - d2 - R2) / twoR);            // lib.rs:136
+        }
+        s_ent[e] = v;
+    }
+}
+
+// Staged entries [0, n) (n a multiple of 4) against the NCH chunks of a pass; REM: some lane of the pass takes the
+// remainder rule (rem[c]).  Returns true once every point of the pass is occluded (lib.rs:149-152).
+template <int NCH, bool REM>
+__device__ __forceinline__ bool pt_test(const float4 *s_ent, uint32_t n, const float (&sx)[NCH], const float (&sy)[NCH],
+                                        const float (&sz)[NCH], const bool (&rem)[NCH], bool (&occ)[NCH])
+{
+    for (uint32_t k = 0; k < n; k += 4) {
+        float4 e[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) e[u] = s_ent[k + u];  // (the four LDS reads in flight together)
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                // lib.rs:143-146: mul_add(sx, vx, mul_add(sy, vy, sz * vz)) < limit
+                bool hit = __builtin_fmaf(sx[c], e[u].x, __builtin_fmaf(sy[c], e[u].y, sz[c] * e[u].z)) < e[u].w;
+                if (REM) {
+                    // lib.rs:185-186,206-207: plain products, `<=`
+                    const float dotu = sx[c] * e[u].x + sy[c] * e[u].y + sz[c] * e[u].z;
+                    hit = rem[c] ? dotu <= e[u].w : hit;
+                }
+                occ[c] = occ[c] || hit;
+            }
+        }
+        bool all = true;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) all = all && occ[c];
+        if (ballot64(!all) == 0ull) return true;
+    }
+    return false;
+}
+
+// NCH chunks of 64 points per pass: every staged entry is read once for all of them.
+template <int NCH>
+__global__ __launch_bounds__(256) void k_accessible_points(PtArgs a)
+{
+    const BatchView &b = a.b;
+    __shared__ float4 s_ent[4][kPtStage];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t p = blockIdx.x * 4u + w;
+    if (p >= b.n_atoms) return;
+    const uint32_t row = b.sorted_orig[p];
+    const uint32_t base = b.grids[b.sid_sorted[p]].atom_begin;
+    const float4 me = make_float4(b.x[row], b.y[row], b.z[row], b.radius[row]);
+    const float R = me.w + b.probe;  // lib.rs:101
+    const float R2 = R * R;          // lib.rs:102
+    const float twoR = 2.0f * R;     // lib.rs:136
+    const unsigned long long off = a.offsets[row];
+    const uint32_t K = (uint32_t)(a.offsets[row + 1] - off);
+    const uint2 *ent = a.entries + off;
+    const bool one_stage = K <= kPtStage;
+    if (one_stage && K) {
+        pt_stage(a, ent, 0, K, base, me, R2, twoR, s_ent[w]);
+        wave_lds_fence();
+    }
+
+    const uint32_t n_chunks = (a.n_points + kWave - 1) / kWave;
+    // the points of the next pass are loaded while this one runs (the lattice arrays are zero padded to whole chunks)
+    float nx[NCH], ny[NCH], nz[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const uint32_t pi = (uint32_t)c * kWave + lane;
+        const bool in = (uint32_t)c < n_chunks;
+        nx[c] = in ? a.lx[pi] : 0.0f;
+        ny[c] = in ? a.ly[pi] : 0.0f;
+        nz[c] = in ? a.lz[pi] : 0.0f;
+    }
+    uint32_t exposed = 0;
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += NCH) {
+        float sx[NCH], sy[NCH], sz[NCH];
+        bool occ[NCH], rem[NCH];
+        bool any_rem = false;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            sx[c] = nx[c]; sy[c] = ny[c]; sz[c] = nz[c];
+            const uint32_t pi = (c0 + c) * kWave + lane;
+            occ[c] = pi >= a.n_points;  // lanes past the last point (and chunks past the last): never exposed
+            rem[c] = pi >= a.n_fused;
+            any_rem = any_rem || (rem[c] && !occ[c]);
+            const uint32_t nc = c0 + NCH + c;
+            const bool in = nc < n_chunks;
+            nx[c] = in ? a.lx[nc * kWave + lane] : 0.0f;
+            ny[c] = in ? a.ly[nc * kWave + lane] : 0.0f;
+            nz[c] = in ? a.lz[nc * kWave + lane] : 0.0f;
+        }
+        any_rem = ballot64(any_rem) != 0ull;
+        for (uint32_t s0 = 0; s0 < K; s0 += kPtStage) {
+            const uint32_t n = min(kPtStage, K - s0);
+            if (!one_stage) {
+                wave_lds_fence();  // (every lane is done with the previous stage)
+                pt_stage(a, ent, s0, n, base, me, R2, twoR, s_ent[w]);
+                wave_lds_fence();
+            }
+            const uint32_t n4 = (n + 3u) & ~3u;
+            if (any_rem ? pt_test<NCH, true>(s_ent[w], n4, sx, sy, sz, rem, occ)
+                        : pt_test<NCH, false>(s_ent[w], n4, sx, sy, sz, rem, occ))
+                break;
+        }
+        // the pass's exposed ballots: lanes 0 .. 2 NCH - 1 write its 2 NCH words at once
+        uint32_t word = 0;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            const unsigned long long m = ballot64(!occ[c]);
+            exposed += (uint32_t)__popcll(m);
+            if (lane == 2u * c) word = (uint32_t)m;
+            if (lane == 2u * c + 1u) word = (uint32_t)(m >> 32);
+        }
+        const uint32_t wi = 2u * c0 + lane;
+        if (lane < 2u * NCH && wi < a.words) a.masks[(size_t)row * a.words + wi] = word;
+    }
+    if (lane == 0 && a.sasa)  // lib.rs:220-222
+        a.sasa[row] = ((4.0f * 3.14159274101257324219f) * R2) * (float)exposed * (1.0f / (float)a.n_points);
+}
+
+}  // namespace
+
+// masks[] (and sasa[], if set) of every atom of the binned batch
+void launch_accessible_points(const PtArgs &a, hipStream_t stream)
+{
+    const uint32_t n = a.b.n_atoms;
+    if (!n) return;
+    if (a.n_points <= 2u * kWave) hipLaunchKernelGGL(k_accessible_points<2>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_accessible_points<4>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
+}
+
+}  // namespace rsasa

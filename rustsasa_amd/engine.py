@@ -250,6 +250,38 @@ class Context:
         offsets, entries = self.precompute_neighbors(x, y, z, radius, ids, probe_radius, max_radius, active_indices)
         return [entries[int(offsets[i]):int(offsets[i + 1])] for i in range(offsets.shape[0] - 1)]
 
+    # ---- accessible sphere points (the decisions behind each SASA value, reference src/lib.rs:96-223) ----
+    def accessible_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
+        """rsasa_accessible_points: (words uint32[N, (n_points + 31) // 32], sasa float32[N]); bit p & 31 of word p >> 5 of
+        row i is 1 when point p of sphere_points(n_points) is accessible on atom i.  sasa equals calculate_sasa_soa."""
+        n_points = _n_points(n_points)
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        words = np.zeros((x.shape[0], _words(n_points)), np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.rsasa_accessible_points(
+            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, ptr(words),
+            ptr(sasa)))
+        return words, sasa
+
+    def accessible_points_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
+                                n_points: int = 100):
+        """rsasa_accessible_points_batch: accessible_points of every structure (one grid each), rows in batch order."""
+        n_points = _n_points(n_points)
+        so = _offsets("structure_offsets", structure_offsets)
+        n_struct = so.shape[0] - 1
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
+        words = np.zeros((x.shape[0], _words(n_points)), np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.rsasa_accessible_points_batch(
+            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
+            ptr(words), ptr(sasa)))
+        return words, sasa
+
+    def surface_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
+        """The accessible points themselves: (atom_index uint32[M], xyz float32[M, 3]), see surface_points()."""
+        words, _ = self.accessible_points(x, y, z, radius, ids, probe_radius, n_points)
+        return surface_points(words, x, y, z, radius, probe_radius, n_points)
+
     # ---- MD trajectory: one topology, many frames --------------------------
     def calculate_sasa_trajectory(self, xyz, radius, ids=None, probe_radius: float = 1.4,
                                   n_points: int = 100, residue_offsets=None, want_atoms: bool = True):
@@ -352,6 +384,45 @@ class Context:
         return int(n.value)
 
 
+def _n_points(n_points) -> int:
+    n = int(n_points)
+    if n != n_points or n < 1:
+        raise ValueError(f"n_points must be a positive integer, not {n_points!r}")
+    return n
+
+
+def _words(n_points: int) -> int:
+    return (n_points + 31) // 32
+
+
+def unpack_points(words, n_points: int) -> np.ndarray:
+    """Masks of accessible_points as bool[N, n_points] (column p: point p of sphere_points(n_points))."""
+    n_points = _n_points(n_points)
+    words = np.ascontiguousarray(words, dtype="<u4")
+    if words.ndim != 2 or words.shape[1] != _words(n_points):
+        raise ValueError(f"words must have shape [N, {_words(n_points)}] for {n_points} points")
+    bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")
+    return bits[:, :n_points].astype(bool)
+
+
+def surface_points(words, x, y, z, radius, probe_radius: float = 1.4, n_points: int = 100):
+    """The accessible points of masks `words` (accessible_points of these columns): (atom_index uint32[M],
+    xyz float32[M, 3]), atoms in order and each atom's points in lattice order.  A point is c + R * s in float32
+    (no FMA), R = radius + probe_radius, s the point of sphere_points(n_points) - the reference's sphere
+    (src/lib.rs:101, 43-66)."""
+    mask = unpack_points(words, n_points)
+    x, y, z, radius, _ = _columns(x, y, z, radius, None)
+    if x.shape[0] != mask.shape[0]:
+        raise ValueError(f"words has {mask.shape[0]} rows but the columns hold {x.shape[0]} atoms")
+    atom, p = np.nonzero(mask)
+    sx, sy, sz = sphere_points(n_points)
+    R = radius[atom] + np.float32(probe_radius)
+    xyz = np.empty((atom.shape[0], 3), np.float32)
+    for k, (c, s) in enumerate(((x, sx), (y, sy), (z, sz))):
+        xyz[:, k] = c[atom] + R * s[p]
+    return atom.astype(np.uint32), xyz
+
+
 def make_atoms(x, y, z, radius, ids) -> np.ndarray:
     """Packs SoA columns into rsasa_atom_t records."""
     a = np.zeros(len(x), ATOM_DTYPE)
@@ -363,4 +434,5 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
     return a
 
 
-__all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
+__all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
+           "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
