@@ -37,7 +37,7 @@ extern "C" {
  * nothing else changed, nothing removed.
  * Additive under 4 (callers detect them by symbol): rsasa_neighbor_t, rsasa_precompute_neighbors,
  * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL; rsasa_accessible_points,
- * rsasa_accessible_points_batch. */
+ * rsasa_accessible_points_batch; rsasa_contact_points, rsasa_contact_points_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -49,8 +49,8 @@ typedef enum rsasa_status {
     RSASA_ERR_GRID_TOO_LARGE = -5,   /* a structure's cell grid exceeds 2^31 cells (coordinates too sparse) */
     RSASA_ERR_INTERNAL = -6,
     RSASA_ERR_QUEUE_FULL = -7,       /* rsasa_host_batch_enqueue: eight batches are queued and not yet waited for */
-    RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*: out_entries is NULL or holds fewer entries than
-                                        out_offsets[n] (which has been written) */
+    RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*: out_entries is NULL or holds
+                                        fewer entries than out_offsets[n] (which has been written) */
 } rsasa_status;
 
 /* Mirrors `Atom` (reference src/structures/atomic.rs:13-24) without the
@@ -408,6 +408,73 @@ int rsasa_accessible_points_batch(rsasa_context_t *ctx,
                                   const uint32_t *structure_offsets, size_t n_structures,
                                   float probe_radius, size_t n_points,
                                   uint32_t *out_masks, float *out_atom_sasa);
+
+/* ---- contact counts ----------------------------------------------------- */
+
+/* WHICH neighbour buries which part of an atom: per entry of each atom's
+ * neighbour list, how many of the atom's sphere points it occludes - contact
+ * surfaces between atoms, residues or chains, the atoms of a partner that bury
+ * a residue, the area an atom regains when one neighbour goes.
+ *
+ * The lists are those of calculate_sasa_internal: out_offsets and out_entries
+ * are byte for byte what rsasa_precompute_neighbors[_batch] returns with
+ * max_radius = NaN (each list sorted by (d^2, idx); in the batch form idx is
+ * the index within the structure).  For atom i, entry e of its list and
+ * lattice point p, hit(e, p) is the test rsasa_accessible_points documents:
+ * fmaf(sx, vx, fmaf(sy, vy, sz*vz)) < limit for p < n_fused, and
+ * (sx*vx + sy*vy) + sz*vz <= limit after that, with
+ * n_fused = n_points - n_points % W (W the context's lane count).
+ *   out_covered[e]   = #{p : hit(e, p)}: the points e occludes, whatever the
+ *                      other entries do;
+ *   out_exclusive[e] = #{p : hit(e, p) and hit(e', p) for no other entry e'}:
+ *                      the points only e occludes.
+ * Both are uint32, aligned with out_entries, and do not depend on the list's
+ * order; entries with out_covered == 0 are kept.  out_sasa[i] (nullable) is bit
+ * for bit rsasa_calculate_sasa_batch: k = n_points - #{p : some hit} is n_points
+ * minus the popcount of rsasa_accessible_points.  A count k is an area of
+ * ((12.566371f * (R*R)) * (float)k) * (1.0f / (float)n_points) square
+ * angstroms, R = radius + probe of the atom that owns the list (lib.rs:220-222);
+ * out_exclusive[e] as an area is what atom i's SASA grows by when atom idx is
+ * deleted from the structure, as long as the deletion leaves the structure's
+ * largest radius unchanged.
+ *
+ * Sizing, as the neighbour calls: out_offsets is always written (on success
+ * and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_entries, out_covered or
+ * out_exclusive is NULL, or entries_capacity < out_offsets[n], nothing else is
+ * written and RSASA_ERR_BUFFER_TOO_SMALL is returned: call once to size,
+ * allocate, call again.
+ *
+ * Everything else is as rsasa_accessible_points*: the argument errors; the
+ * "Non-finite input" paragraph (a NaN coordinate: an empty list, nobody's
+ * neighbour; a NaN radius: an empty list and a NaN threshold in the lists of
+ * others, so counts of 0 there; an infinite coordinate:
+ * RSASA_ERR_GRID_TOO_LARGE, the context stays usable); synchronous, in the
+ * neighbour calls' workspace on the context's first stream, so device batches
+ * in flight (rsasa_batch_enqueue) are neither waited for nor disturbed.  The
+ * lists stay on the device between the neighbour search and the counts. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).
+ * out_offsets: [n_atoms + 1]; out_entries, out_covered, out_exclusive:
+ * [entries_capacity]; out_sasa: [n_atoms] or NULL. */
+int rsasa_contact_points(rsasa_context_t *ctx,
+                         const float *x, const float *y, const float *z, const float *radius,
+                         const uint64_t *id, size_t n_atoms,
+                         float probe_radius, size_t n_points,
+                         uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                         uint32_t *out_covered, uint32_t *out_exclusive, size_t entries_capacity,
+                         float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each); out_offsets
+ * is batch-global [structure_offsets[n_structures] + 1]. */
+int rsasa_contact_points_batch(rsasa_context_t *ctx,
+                               const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id,
+                               const uint32_t *structure_offsets, size_t n_structures,
+                               float probe_radius, size_t n_points,
+                               uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                               uint32_t *out_covered, uint32_t *out_exclusive, size_t entries_capacity,
+                               float *out_atom_sasa);
 
 /* ---- measurement ------------------------------------------------------- */
 

@@ -214,6 +214,14 @@ struct PtArgs {
     float *sasa;                        // [n_atoms] or null: ((4 pi R^2) popcount) / n_points (lib.rs:220-222)
 };
 
+// ---- contact counts (points.hip, rsasa_contact_points*) ----
+// The same lists and lattice (p.masks unused), per-entry counts out, aligned with NbArgs::out.
+struct CtArgs {
+    PtArgs p;                           // p.sasa: [n_atoms] or null, ((4 pi R^2) k) / n_points with k the points no entry hits
+    uint32_t *covered;                  // [offsets[n_atoms]]: points of the atom the entry hits
+    uint32_t *exclusive;                // [offsets[n_atoms]]: points of the atom the entry hits and no other entry of the list does
+};
+
 // Grid and status of a one-structure batch, computed by the host and handed to k_sort_window<true> as
 // kernel arguments.
 struct SingleJob {
@@ -274,6 +282,8 @@ void launch_neighbor_count(const NbArgs &a, hipStream_t stream);
 void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
 // The point masks (points.hip) from those lists.
 void launch_accessible_points(const PtArgs &a, hipStream_t stream);
+// The per-entry point counts (points.hip) from those lists.
+void launch_contact_points(const CtArgs &c, hipStream_t stream);
 // Pinned 24-byte atom records (x, y, z, r, id) -> device columns, and `hdr_bytes` of header beside them (combine.cpp).
 void launch_unpack_atoms(const void *records, uint32_t n_atoms, float *x, float *y, float *z, float *r, uint64_t *id,
                          const void *hdr_src, void *hdr_dst, uint32_t hdr_bytes, hipStream_t stream);

@@ -194,6 +194,65 @@ int pt_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     return RSASA_OK;
 }
 
+// ---- contact counts (rsasa_contact_points*) ----
+
+// One run of the contact counts: the lists of pt_run, sized and copied out as by nb_run, and k_contact_points' counts
+// of every entry beside them.
+int ct_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *so, size_t S, size_t N, float probe, size_t n_points, uint64_t *out_offsets,
+           rsasa_neighbor_t *out_entries, uint32_t *out_covered, uint32_t *out_exclusive, size_t cap, float *out_sasa)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    NbArgs a{};
+    NbInfo info{};
+    if ((rc = nb_count(ctx, x, y, z, r, id, so, S, N, nullptr, probe, __builtin_nanf(""), out_offsets, a, info))) return rc;
+    if (!out_entries || !out_covered || !out_exclusive || cap < info.total)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "an entry buffer is NULL or holds fewer entries than out_offsets[n]");
+    if (info.total && ((rc = nb_fill(ctx, a, info)) || (rc = reserve(ctx, ctx->ct_covered, info.total * 4)) ||
+                       (rc = reserve(ctx, ctx->ct_exclusive, info.total * 4))))
+        return rc;
+    size_t padded = 0;
+    if ((rc = pt_lattice(ctx, n_points, padded)) || (out_sasa && (rc = reserve(ctx, ctx->pt_sasa, N * 4)))) return rc;
+    CtArgs c{};
+    c.p.b = a.b;
+    c.p.offsets = a.offsets;
+    c.p.entries = (const uint2 *)ctx->nb_entries.p;  // (none of these three is read when every list is empty)
+    c.covered = (uint32_t *)ctx->ct_covered.p;
+    c.exclusive = (uint32_t *)ctx->ct_exclusive.p;
+    const float *lat = (const float *)ctx->pt_lattice.p;
+    c.p.lx = lat; c.p.ly = lat + padded; c.p.lz = lat + 2 * padded;
+    c.p.n_points = (uint32_t)n_points;
+    c.p.n_fused = (uint32_t)(n_points - n_points % (size_t)ctx->simd_width);
+    c.p.sasa = out_sasa ? (float *)ctx->pt_sasa.p : nullptr;
+    hipStream_t st = ctx->stream;
+    launch_contact_points(c, st);
+    RS_HIP(ctx, hipGetLastError());
+    if (info.total) {
+        RS_HIP(ctx, hipMemcpyAsync(out_entries, c.p.entries, info.total * 8, hipMemcpyDeviceToHost, st));
+        RS_HIP(ctx, hipMemcpyAsync(out_covered, c.covered, info.total * 4, hipMemcpyDeviceToHost, st));
+        RS_HIP(ctx, hipMemcpyAsync(out_exclusive, c.exclusive, info.total * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, c.p.sasa, N * 4, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+// The argument checks of rsasa_accessible_points*, and out_offsets.
+int ct_check(rsasa_context *ctx, size_t N, const float *x, const float *y, const float *z, const float *radius,
+             size_t n_points, const uint64_t *out_offsets)
+{
+    if (!out_offsets || (N && (!x || !y || !z || !radius))) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
+    if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    return RSASA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -281,6 +340,39 @@ int rsasa_accessible_points_batch(rsasa_context_t *ctx, const float *x, const fl
     if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
     if (N && (!x || !y || !z || !radius || !out_masks)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
     return pt_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_masks, out_atom_sasa);
+}
+
+int rsasa_contact_points(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                         const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, uint64_t *out_offsets,
+                         rsasa_neighbor_t *out_entries, uint32_t *out_covered, uint32_t *out_exclusive,
+                         size_t entries_capacity, float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if ((rc = ct_check(ctx, n_atoms, x, y, z, radius, n_points, out_offsets))) return rc;
+    const uint32_t so[2] = {0u, (uint32_t)n_atoms};
+    return ct_run(ctx, x, y, z, radius, id, so, 1, n_atoms, probe_radius, n_points, out_offsets, out_entries, out_covered,
+                  out_exclusive, entries_capacity, out_sasa);
+}
+
+int rsasa_contact_points_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures,
+                               float probe_radius, size_t n_points, uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                               uint32_t *out_covered, uint32_t *out_exclusive, size_t entries_capacity,
+                               float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!structure_offsets) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_structures >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "too many structures");
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1])
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (n_structures && structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets[0] must be 0");
+    if ((rc = ct_check(ctx, N, x, y, z, radius, n_points, out_offsets))) return rc;
+    return ct_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_offsets,
+                  out_entries, out_covered, out_exclusive, entries_capacity, out_atom_sasa);
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 //                         kPtStage entries at a time, and every lane tests its points against each staged entry.  A
 //                         pass stops once its ballot of still-exposed lanes is empty.  Each chunk's exposed ballot is
 //                         two 32-bit words of the mask.
+//   k_contact_points      (rsasa_contact_points*) the same layout, no early exit: per entry of the list, the points it
+//                         hits (covered) and those it alone hits (exclusive), from two sweeps of the list per pass.
 //
 // Points [0, n_fused) take the fused rule - mul_add(sx, vx, mul_add(sy, vy, sz * vz)) < limit (lib.rs:143-146) -, the
 // rest the remainder rule - plain products, `<=` (lib.rs:185-186,206-207).  Both rules are ORs over the list, so the
@@ -155,6 +157,147 @@ __global__ __launch_bounds__(256) void k_accessible_points(PtArgs a)
         a.sasa[row] = ((4.0f * 3.14159274101257324219f) * R2) * (float)exposed * (1.0f / (float)a.n_points);
 }
 
+// ---- contact counts (rsasa_contact_points*) ----
+
+// Staged entries [0, n) (n a multiple of 4) against the NCH chunks of a pass: entry k's hits on the points `gate`
+// admits are counted into s_cnt[k].  FIRST (the first sweep): every hit also marks its point hit once, or twice once
+// it was hit before.
+template <int NCH, bool REM, bool FIRST>
+__device__ __forceinline__ void ct_test(const float4 *s_ent, uint32_t n, const float (&sx)[NCH], const float (&sy)[NCH],
+                                        const float (&sz)[NCH], const bool (&rem)[NCH], const bool (&gate)[NCH],
+                                        bool (&once)[NCH], bool (&twice)[NCH], uint32_t *s_cnt)
+{
+    const uint32_t lane = lane_id();
+    for (uint32_t k = 0; k < n; k += 4) {
+        float4 e[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) e[u] = s_ent[k + u];
+        uint32_t cnt[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            cnt[u] = 0;
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                // the tests of pt_test (lib.rs:143-146; lib.rs:185-186,206-207)
+                bool hit = __builtin_fmaf(sx[c], e[u].x, __builtin_fmaf(sy[c], e[u].y, sz[c] * e[u].z)) < e[u].w;
+                if (REM) {
+                    const float dotu = sx[c] * e[u].x + sy[c] * e[u].y + sz[c] * e[u].z;
+                    hit = rem[c] ? dotu <= e[u].w : hit;
+                }
+                hit = hit && gate[c];
+                if (FIRST) {
+                    twice[c] = twice[c] || (once[c] && hit);
+                    once[c] = once[c] || hit;
+                }
+                cnt[u] += (uint32_t)__popcll(ballot64(hit));
+            }
+        }
+        // lanes 0 .. 3 write the group's four counts at once
+        const uint32_t mine = lane == 0 ? cnt[0] : lane == 1 ? cnt[1] : lane == 2 ? cnt[2] : cnt[3];
+        if (lane < 4u) s_cnt[k + lane] = mine;
+    }
+}
+
+// One sweep of the whole list (kPtStage entries at a time) for the chunks of a pass: entry e's count goes to dst[e],
+// added to what the earlier passes left there when `add`.
+template <int NCH, bool FIRST>
+__device__ __forceinline__ void ct_sweep(const PtArgs &a, const uint2 *ent, uint32_t K, bool one_stage, uint32_t base,
+                                         const float4 me, float R2, float twoR, float4 *s_ent, uint32_t *s_cnt,
+                                         uint32_t *dst, bool add, bool any_rem, const float (&sx)[NCH],
+                                         const float (&sy)[NCH], const float (&sz)[NCH], const bool (&rem)[NCH],
+                                         const bool (&gate)[NCH], bool (&once)[NCH], bool (&twice)[NCH])
+{
+    for (uint32_t s0 = 0; s0 < K; s0 += kPtStage) {
+        const uint32_t n = min(kPtStage, K - s0);
+        if (!one_stage) {
+            wave_lds_fence();  // (every lane is done with the previous stage)
+            pt_stage(a, ent, s0, n, base, me, R2, twoR, s_ent);
+            wave_lds_fence();
+        }
+        const uint32_t n4 = (n + 3u) & ~3u;
+        if (any_rem) ct_test<NCH, true, FIRST>(s_ent, n4, sx, sy, sz, rem, gate, once, twice, s_cnt);
+        else ct_test<NCH, false, FIRST>(s_ent, n4, sx, sy, sz, rem, gate, once, twice, s_cnt);
+        wave_lds_fence();
+        // coalesced; lane l owns entries l, l + 64, ... in every pass, so what it adds to is its own earlier write
+        for (uint32_t e = lane_id(); e < n; e += kWave) dst[s0 + e] = s_cnt[e] + (add ? dst[s0 + e] : 0u);
+        wave_lds_fence();  // (every lane has read the counts before the next sweep writes them)
+    }
+}
+
+// The layout of k_accessible_points (one wave per cell-sorted atom, lanes over NCH chunks of 64 points per pass, the
+// list staged in LDS by pt_stage), without its early exit.  Per pass, sweep 1 counts each entry's hits (covered) and
+// leaves every lane knowing which of its points one entry hits and which more than one; sweep 2 goes over the list
+// again and counts each entry's hits on the points hit once (exclusive).
+template <int NCH>
+__global__ __launch_bounds__(256) void k_contact_points(CtArgs ct)
+{
+    const PtArgs &a = ct.p;
+    const BatchView &b = a.b;
+    __shared__ float4 s_ent[4][kPtStage];
+    __shared__ uint32_t s_cnt[4][kPtStage];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t p = blockIdx.x * 4u + w;
+    if (p >= b.n_atoms) return;
+    const uint32_t row = b.sorted_orig[p];
+    const uint32_t base = b.grids[b.sid_sorted[p]].atom_begin;
+    const float4 me = make_float4(b.x[row], b.y[row], b.z[row], b.radius[row]);
+    const float R = me.w + b.probe;  // lib.rs:101
+    const float R2 = R * R;          // lib.rs:102
+    const float twoR = 2.0f * R;     // lib.rs:136
+    const unsigned long long off = a.offsets[row];
+    const uint32_t K = (uint32_t)(a.offsets[row + 1] - off);
+    const uint2 *ent = a.entries + off;
+    const bool one_stage = K <= kPtStage;
+    if (one_stage && K) {
+        pt_stage(a, ent, 0, K, base, me, R2, twoR, s_ent[w]);
+        wave_lds_fence();
+    }
+
+    // an empty list: no counts, every point exposed
+    const uint32_t n_chunks = K ? (a.n_points + kWave - 1) / kWave : 0u;
+    float nx[NCH], ny[NCH], nz[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const uint32_t pi = (uint32_t)c * kWave + lane;
+        const bool in = (uint32_t)c < n_chunks;
+        nx[c] = in ? a.lx[pi] : 0.0f;
+        ny[c] = in ? a.ly[pi] : 0.0f;
+        nz[c] = in ? a.lz[pi] : 0.0f;
+    }
+    uint32_t exposed = K ? 0u : a.n_points;
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += NCH) {
+        float sx[NCH], sy[NCH], sz[NCH];
+        bool live[NCH], rem[NCH], once[NCH], twice[NCH], solo[NCH];
+        bool any_rem = false;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            sx[c] = nx[c]; sy[c] = ny[c]; sz[c] = nz[c];
+            const uint32_t pi = (c0 + c) * kWave + lane;
+            live[c] = pi < a.n_points;  // lanes past the last point (and chunks past the last): never counted
+            rem[c] = pi >= a.n_fused;
+            any_rem = any_rem || (rem[c] && live[c]);
+            once[c] = twice[c] = false;
+            const uint32_t nc = c0 + NCH + c;
+            const bool in = nc < n_chunks;
+            nx[c] = in ? a.lx[nc * kWave + lane] : 0.0f;
+            ny[c] = in ? a.ly[nc * kWave + lane] : 0.0f;
+            nz[c] = in ? a.lz[nc * kWave + lane] : 0.0f;
+        }
+        any_rem = ballot64(any_rem) != 0ull;
+        ct_sweep<NCH, true>(a, ent, K, one_stage, base, me, R2, twoR, s_ent[w], s_cnt[w], ct.covered + off, c0 != 0,
+                            any_rem, sx, sy, sz, rem, live, once, twice);
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            solo[c] = once[c] && !twice[c];
+            exposed += (uint32_t)__popcll(ballot64(live[c] && !once[c]));
+        }
+        ct_sweep<NCH, false>(a, ent, K, one_stage, base, me, R2, twoR, s_ent[w], s_cnt[w], ct.exclusive + off, c0 != 0,
+                             any_rem, sx, sy, sz, rem, solo, once, twice);
+    }
+    if (lane == 0 && a.sasa)  // lib.rs:220-222, as k_accessible_points
+        a.sasa[row] = ((4.0f * 3.14159274101257324219f) * R2) * (float)exposed * (1.0f / (float)a.n_points);
+}
+
 }  // namespace
 
 // masks[] (and sasa[], if set) of every atom of the binned batch
@@ -164,6 +307,15 @@ void launch_accessible_points(const PtArgs &a, hipStream_t stream)
     if (!n) return;
     if (a.n_points <= 2u * kWave) hipLaunchKernelGGL(k_accessible_points<2>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(k_accessible_points<4>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
+}
+
+// covered[] and exclusive[] (and p.sasa[], if set) of every atom of the binned batch
+void launch_contact_points(const CtArgs &c, hipStream_t stream)
+{
+    const uint32_t n = c.p.b.n_atoms;
+    if (!n) return;
+    if (c.p.n_points <= 2u * kWave) hipLaunchKernelGGL(k_contact_points<2>, dim3(cdiv(n, 4)), dim3(256), 0, stream, c);
+    else hipLaunchKernelGGL(k_contact_points<4>, dim3(cdiv(n, 4)), dim3(256), 0, stream, c);
 }
 
 }  // namespace rsasa

@@ -277,6 +277,51 @@ class Context:
             ptr(words), ptr(sasa)))
         return words, sasa
 
+    # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
+    def _contact_call(self, call, n_atoms: int):
+        """_neighbor_call with the two count columns beside the entries: call(offsets, entries, covered, exclusive,
+        capacity); returns (offsets, entries, covered uint32[total], exclusive uint32[total])."""
+        counts = []
+
+        def sized(offsets, entries, cap):
+            counts[:] = [np.empty(cap, np.uint32), np.empty(cap, np.uint32)]
+            return call(offsets, entries, counts[0], counts[1], cap)
+        offsets, entries = self._neighbor_call(sized, n_atoms)
+        total = entries.shape[0]
+        return offsets, entries, counts[0][:total], counts[1][:total]
+
+    def contact_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
+        """rsasa_contact_points: (offsets uint64[N + 1], entries NEIGHBOR_DTYPE[total], covered uint32[total],
+        exclusive uint32[total], sasa float32[N]).  offsets / entries are precompute_neighbors(max_radius=None); for
+        entry e of atom i's list, covered[e] counts the points of sphere_points(n_points) on atom i that the entry
+        occludes, exclusive[e] those that no other entry of the list occludes.  sasa equals calculate_sasa_soa;
+        contact_areas() turns counts into A^2."""
+        n_points = _n_points(n_points)
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        sasa = np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, entries, covered, exclusive, cap):
+            return self._lib.rsasa_contact_points(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points,
+                ptr(offsets), ptr(entries), ptr(covered), ptr(exclusive), cap, ptr(sasa))
+        return self._contact_call(call, x.shape[0]) + (sasa,)
+
+    def contact_points_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
+                             n_points: int = 100):
+        """rsasa_contact_points_batch: contact_points of every structure (one grid each); offsets over the whole batch,
+        idx the index within the structure."""
+        n_points = _n_points(n_points)
+        so = _offsets("structure_offsets", structure_offsets)
+        n_struct = so.shape[0] - 1
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
+        sasa = np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, entries, covered, exclusive, cap):
+            return self._lib.rsasa_contact_points_batch(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
+                ptr(offsets), ptr(entries), ptr(covered), ptr(exclusive), cap, ptr(sasa))
+        return self._contact_call(call, x.shape[0]) + (sasa,)
+
     def surface_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
         """The accessible points themselves: (atom_index uint32[M], xyz float32[M, 3]), see surface_points()."""
         words, _ = self.accessible_points(x, y, z, radius, ids, probe_radius, n_points)
@@ -423,6 +468,27 @@ def surface_points(words, x, y, z, radius, probe_radius: float = 1.4, n_points: 
     return atom.astype(np.uint32), xyz
 
 
+def contact_areas(counts, offsets, radius, probe_radius: float = 1.4, n_points: int = 100) -> np.ndarray:
+    """Counts of contact_points (covered or exclusive) as areas, float32[total] in A^2: the reference's
+    ((4 pi R^2) k) / n_points in float32 (src/lib.rs:220-222), k the count and R = radius + probe_radius of the atom
+    whose list holds the entry (row i of `offsets`, radius[i])."""
+    n_points = _n_points(n_points)
+    radius = _f32(radius)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    if radius.ndim != 1 or offsets.ndim != 1 or offsets.shape[0] != radius.shape[0] + 1:
+        raise ValueError(f"offsets must be a 1-D array of {radius.shape[0] + 1} entries (one per atom, and the end)")
+    sizes = np.diff(offsets.astype(np.int64))
+    if offsets[0] != 0 or (sizes < 0).any():
+        raise ValueError("offsets must be non-decreasing from 0")
+    if counts.ndim != 1 or counts.shape[0] != int(offsets[-1]):
+        raise ValueError(f"counts must be a 1-D array of offsets[-1] = {int(offsets[-1])} entries")
+    R = radius[np.repeat(np.arange(radius.shape[0]), sizes)] + np.float32(probe_radius)
+    with np.errstate(invalid="ignore"):
+        return ((np.float32(4.0) * np.float32(np.pi)) * (R * R)) * counts.astype(np.float32) * \
+            (np.float32(1.0) / np.float32(n_points))
+
+
 def make_atoms(x, y, z, radius, ids) -> np.ndarray:
     """Packs SoA columns into rsasa_atom_t records."""
     a = np.zeros(len(x), ATOM_DTYPE)
@@ -435,4 +501,4 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 
 
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
-           "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
+           "contact_areas", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
