@@ -16,7 +16,7 @@ import tie_cases as tc
 
 pytestmark = pytest.mark.gpu
 
-WS = (1, 8, 16)
+WS = (1, 4, 8, 16)
 N_POINTS = (100, 101, 127, 960)
 PROBES = (1.4, 3.0)
 FIXTURES = ["example.cif:vdw", "1jcd.pdb", "151L_H3.pdb", "bad_seqadv_1A06.pdb", "example.cif"]
