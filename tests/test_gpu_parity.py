@@ -325,7 +325,8 @@ def test_full_proteome_every_atom_and_residue(ctx):
 def test_uniform_1m_atoms_960_points_full_size(ctx):
     """BASELINE config 5 at FULL size: one structure of 1 000 000 atoms, 960 points, AtomLevel.
     65 536 atoms or more: the batch-wide (tail) binning route, which the 60 000-atom case above
-    does not take."""
+    does not take.  Its grid has 636 056 cells (86^3): below one scan tile per workgroup, which
+    test_gpu_tail_edges.py goes past."""
     b = bw.synthetic_uniform(1_000_000, seed=5)
     atom, _, k = _device_run(ctx, b, n_points=960, want_res=False)
     want, _, want_k = po.calculate_sasa_internal(b.x, b.y, b.z, b.radius, b.ids, PROBE, 960, 8,
