@@ -37,7 +37,8 @@ extern "C" {
  * nothing else changed, nothing removed.
  * Additive under 4 (callers detect them by symbol): rsasa_neighbor_t, rsasa_precompute_neighbors,
  * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL; rsasa_accessible_points,
- * rsasa_accessible_points_batch; rsasa_contact_points, rsasa_contact_points_batch. */
+ * rsasa_accessible_points_batch; rsasa_contact_points, rsasa_contact_points_batch; rsasa_group_contacts,
+ * rsasa_group_contacts_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -50,7 +51,8 @@ typedef enum rsasa_status {
     RSASA_ERR_INTERNAL = -6,
     RSASA_ERR_QUEUE_FULL = -7,       /* rsasa_host_batch_enqueue: eight batches are queued and not yet waited for */
     RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*: out_entries is NULL or holds
-                                        fewer entries than out_offsets[n] (which has been written) */
+                                        fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
+                                        the same for its row buffers */
 } rsasa_status;
 
 /* Mirrors `Atom` (reference src/structures/atomic.rs:13-24) without the
@@ -475,6 +477,85 @@ int rsasa_contact_points_batch(rsasa_context_t *ctx,
                                uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
                                uint32_t *out_covered, uint32_t *out_exclusive, size_t entries_capacity,
                                float *out_atom_sasa);
+
+/* ---- group contacts ----------------------------------------------------- */
+
+/* WHICH partner buries which part of an atom, above the level of single
+ * atoms: every atom carries a uint32 group label (chain, residue, ligand,
+ * anything), and per atom and partner group the call counts the points the
+ * partner takes - buried surface on complex formation per atom, residue or
+ * chain, the chain x chain or residue x residue interface matrix, what an atom
+ * regains when a ligand or a chain is removed.  The area one group buries is a
+ * UNION over its atoms: sums of rsasa_contact_points' per-entry counts over a
+ * group count every point twice that two of its atoms hit.
+ *
+ * For atom i, L(i) is its list as rsasa_contact_points uses it (max_radius =
+ * NaN), g(.) are the labels - compared within one structure only - and
+ * hit(e, p) is the test rsasa_accessible_points documents (the fused rule for
+ * p < n_fused, the remainder rule after it, W the context's lane count).
+ *   self(p)          = some entry e of L(i) with g(idx_e) == g(i) has hit(e, p);
+ *   out_self_free[i] = #{p : !self(p)}: the accessible points of atom i with
+ *                      only its own group present (n_points if no entry shares
+ *                      its label);
+ *   out_free[i]      = #{p : no entry hits p}: the popcount of
+ *                      rsasa_accessible_points;
+ *   out_sasa[i]      (nullable) bit for bit rsasa_calculate_sasa_batch.
+ * Atom i has one row per DISTINCT FOREIGN label h among the entries of L(i), in
+ * ascending unsigned order of h, in CSR form: its rows are
+ * [out_offsets[i], out_offsets[i + 1]), out_groups[row] = h.  With
+ * cov_h(p) = some entry labelled h has hit(e, p):
+ *   out_buried[row]  = #{p : cov_h(p) && !self(p)}: what group h alone takes
+ *                      from atom i of the isolated group g(i) - the pairwise
+ *                      interface, A+B against A;
+ *   out_only[row]    = #{p : cov_h(p) && !self(p) && cov_h'(p) for no other
+ *                      foreign h'}: what atom i regains in the whole structure
+ *                      when group h is deleted.
+ * Rows whose counts are 0 are kept (a neighbour with a NaN radius, a candidate
+ * that hits nothing).  Nothing depends on the list's order.  Counts are areas
+ * by the expression given for rsasa_contact_points, R that of atom i.  As
+ * there, the statements about isolated groups and deletions are exact as long
+ * as the smaller structure has the whole structure's largest radius (the
+ * candidate rule depends on it).
+ *
+ * Sizing, as the neighbour and contact calls: out_offsets is always written (on
+ * success and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_groups, out_buried or
+ * out_only is NULL, or rows_capacity < out_offsets[n], nothing else is written
+ * and RSASA_ERR_BUFFER_TOO_SMALL is returned: call once to size, allocate,
+ * call again.  group, out_self_free and out_free are required where there are
+ * atoms: NULL returns RSASA_ERR_INVALID_ARGUMENT.
+ *
+ * Everything else is as rsasa_contact_points*: the argument errors; non-finite
+ * input (a NaN coordinate: no rows, n_points everywhere; a NaN radius: the
+ * same, and rows of 0 in the lists of others; an infinite coordinate:
+ * RSASA_ERR_GRID_TOO_LARGE, the context stays usable); synchronous, in the
+ * neighbour calls' workspace on the context's first stream, so device batches
+ * in flight are neither waited for nor disturbed.  The lists stay on the
+ * device; only the labels go up and the rows and per-atom counts come down. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).
+ * group: [n_atoms]; out_offsets: [n_atoms + 1]; out_groups, out_buried,
+ * out_only: [rows_capacity]; out_self_free, out_free: [n_atoms]; out_sasa:
+ * [n_atoms] or NULL. */
+int rsasa_group_contacts(rsasa_context_t *ctx,
+                         const float *x, const float *y, const float *z, const float *radius,
+                         const uint64_t *id, const uint32_t *group, size_t n_atoms,
+                         float probe_radius, size_t n_points,
+                         uint64_t *out_offsets, uint32_t *out_groups,
+                         uint32_t *out_buried, uint32_t *out_only, size_t rows_capacity,
+                         uint32_t *out_self_free, uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each); out_offsets
+ * is batch-global [structure_offsets[n_structures] + 1].  Labels never match
+ * across structures: lists never cross them. */
+int rsasa_group_contacts_batch(rsasa_context_t *ctx,
+                               const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, const uint32_t *group,
+                               const uint32_t *structure_offsets, size_t n_structures,
+                               float probe_radius, size_t n_points,
+                               uint64_t *out_offsets, uint32_t *out_groups,
+                               uint32_t *out_buried, uint32_t *out_only, size_t rows_capacity,
+                               uint32_t *out_self_free, uint32_t *out_free, float *out_atom_sasa);
 
 /* ---- measurement ------------------------------------------------------- */
 

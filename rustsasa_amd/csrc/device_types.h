@@ -222,6 +222,23 @@ struct CtArgs {
     uint32_t *exclusive;                // [offsets[n_atoms]]: points of the atom the entry hits and no other entry of the list does
 };
 
+// ---- group contacts (points.hip, rsasa_group_contacts*) ----
+// The same lists and lattice (p.masks unused) and a label per atom: k_group_order reorders every list by label and counts
+// its rows (one per distinct foreign label), the host scans the counts into row_offsets, k_group_points fills the rows.
+struct GpArgs {
+    PtArgs p;                           // p.sasa: [n_atoms] or null, as CtArgs
+    const uint32_t *group;              // [n_atoms] the labels, input order
+    uint2 *sorted;                      // [offsets[n_atoms]] every list again: its own-group entries first, then the others
+                                        // by (label, position in the list)
+    uint32_t *sorted_group;             // [offsets[n_atoms]] the labels of those entries
+    uint32_t *n_own;                    // [n_atoms] own-group entries of the list
+    uint32_t *n_rows;                   // [n_atoms] distinct foreign labels of the list
+    const unsigned long long *row_offsets;  // [n_atoms + 1] exclusive scan of n_rows
+    uint32_t *groups, *buried, *only;   // [row_offsets[n_atoms]] a row's label, and the points of the atom its own group leaves
+                                        // free that the label hits / that it alone among the foreign labels hits
+    uint32_t *self_free, *free;         // [n_atoms] points no own-group entry hits / no entry hits
+};
+
 // Grid and status of a one-structure batch, computed by the host and handed to k_sort_window<true> as
 // kernel arguments.
 struct SingleJob {
@@ -284,6 +301,11 @@ void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t str
 void launch_accessible_points(const PtArgs &a, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);
+// The 64-bit exclusive scan of the count pass by itself (neighbors.hip): a.counts -> a.offsets[0 .. n_atoms], totals -> a.info.
+void launch_neighbor_scan(const NbArgs &a, hipStream_t stream);
+// Group contacts (points.hip): the lists in label order and their row counts; then, with GpArgs::row_offsets, the rows.
+void launch_group_order(const GpArgs &g, hipStream_t stream);
+void launch_group_points(const GpArgs &g, hipStream_t stream);
 // Pinned 24-byte atom records (x, y, z, r, id) -> device columns, and `hdr_bytes` of header beside them (combine.cpp).
 void launch_unpack_atoms(const void *records, uint32_t n_atoms, float *x, float *y, float *z, float *r, uint64_t *id,
                          const void *hdr_src, void *hdr_dst, uint32_t hdr_bytes, hipStream_t stream);

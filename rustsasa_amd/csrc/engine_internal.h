@@ -456,6 +456,10 @@ struct rsasa_context {
     size_t pt_lattice_points = 0;  // the point count pt_lattice holds (0: none)
     // rsasa_contact_points*: the per-entry counts of the last call (the lists, lattice and values are the buffers above)
     DeviceBuffer ct_covered, ct_exclusive;
+    // rsasa_group_contacts*: the labels, the lists in label order with their own-group and row counts, the row offsets,
+    // and the rows and per-atom counts of the last call
+    DeviceBuffer gp_group, gp_sorted, gp_sorted_group, gp_own, gp_nrows, gp_offsets, gp_groups, gp_buried, gp_only, gp_self_free,
+        gp_free;
 };
 
 namespace rsasa {

@@ -1,7 +1,8 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h): the
 // batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws), then
 // neighbors.hip counts, scans and fills the lists.  The accessible-point entry points (rsasa_accessible_points /
-// _batch) run the same stages and hand the lists, still on the device, to points.hip.  Host code only.
+// _batch) run the same stages and hand the lists, still on the device, to points.hip; so do the contact counts
+// (rsasa_contact_points*) and the group contacts (rsasa_group_contacts*).  Host code only.
 #include "engine_internal.h"
 
 namespace {
@@ -253,6 +254,96 @@ int ct_check(rsasa_context *ctx, size_t N, const float *x, const float *y, const
     return RSASA_OK;
 }
 
+// ---- group contacts (rsasa_group_contacts*) ----
+
+// One run of the group contacts: the lists of pt_run stay on the device; k_group_order puts each in label order and
+// counts its rows, the scan of the neighbour counts turns those into out_offsets, the caller's row buffers are checked
+// against out_offsets[N] as nb_run checks its entries, and k_group_points fills the rows.
+int gp_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *group, const uint32_t *so, size_t S, size_t N, float probe, size_t n_points, uint64_t *out_offsets,
+           uint32_t *out_groups, uint32_t *out_buried, uint32_t *out_only, size_t cap, uint32_t *out_self_free,
+           uint32_t *out_free, float *out_sasa)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    hipStream_t st = ctx->stream;
+    NbArgs a{};
+    NbInfo info{};
+    if ((rc = nb_count(ctx, x, y, z, r, id, so, S, N, nullptr, probe, __builtin_nanf(""), nullptr, a, info))) return rc;
+    if (info.total && ((rc = nb_fill(ctx, a, info)) || (rc = reserve(ctx, ctx->gp_sorted, info.total * 8)) ||
+                       (rc = reserve(ctx, ctx->gp_sorted_group, info.total * 4))))
+        return rc;
+    if ((rc = reserve(ctx, ctx->gp_group, N * 4)) || (rc = reserve(ctx, ctx->gp_own, N * 4)) ||
+        (rc = reserve(ctx, ctx->gp_nrows, N * 4)) || (rc = reserve(ctx, ctx->gp_offsets, (N + 1) * 8)))
+        return rc;
+    RS_HIP(ctx, hipMemcpyAsync(ctx->gp_group.p, group, N * 4, hipMemcpyHostToDevice, st));
+    GpArgs g{};
+    g.p.b = a.b;
+    g.p.offsets = a.offsets;
+    g.p.entries = (const uint2 *)ctx->nb_entries.p;  // (neither the lists nor their copies are read when every list is empty)
+    g.group = (const uint32_t *)ctx->gp_group.p;
+    g.sorted = (uint2 *)ctx->gp_sorted.p;
+    g.sorted_group = (uint32_t *)ctx->gp_sorted_group.p;
+    g.n_own = (uint32_t *)ctx->gp_own.p;
+    g.n_rows = (uint32_t *)ctx->gp_nrows.p;
+    g.row_offsets = (const unsigned long long *)ctx->gp_offsets.p;
+    launch_group_order(g, st);
+    NbArgs scan = a;  // (the neighbour run has read its parts and its info)
+    scan.counts = g.n_rows;
+    scan.offsets = (unsigned long long *)ctx->gp_offsets.p;
+    launch_neighbor_scan(scan, st);
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, hipMemcpyAsync(out_offsets, g.row_offsets, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    const uint64_t n_rows = out_offsets[N];
+    if (!out_groups || !out_buried || !out_only || cap < n_rows)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "a row buffer is NULL or holds fewer rows than out_offsets[n]");
+    size_t padded = 0;
+    if ((n_rows && ((rc = reserve(ctx, ctx->gp_groups, n_rows * 4)) || (rc = reserve(ctx, ctx->gp_buried, n_rows * 4)) ||
+                    (rc = reserve(ctx, ctx->gp_only, n_rows * 4)))) ||
+        (rc = reserve(ctx, ctx->gp_self_free, N * 4)) || (rc = reserve(ctx, ctx->gp_free, N * 4)) ||
+        (rc = pt_lattice(ctx, n_points, padded)) || (out_sasa && (rc = reserve(ctx, ctx->pt_sasa, N * 4))))
+        return rc;
+    g.groups = (uint32_t *)ctx->gp_groups.p;
+    g.buried = (uint32_t *)ctx->gp_buried.p;
+    g.only = (uint32_t *)ctx->gp_only.p;
+    g.self_free = (uint32_t *)ctx->gp_self_free.p;
+    g.free = (uint32_t *)ctx->gp_free.p;
+    const float *lat = (const float *)ctx->pt_lattice.p;
+    g.p.lx = lat; g.p.ly = lat + padded; g.p.lz = lat + 2 * padded;
+    g.p.n_points = (uint32_t)n_points;
+    g.p.n_fused = (uint32_t)(n_points - n_points % (size_t)ctx->simd_width);
+    g.p.sasa = out_sasa ? (float *)ctx->pt_sasa.p : nullptr;
+    launch_group_points(g, st);
+    RS_HIP(ctx, hipGetLastError());
+    if (n_rows) {
+        RS_HIP(ctx, hipMemcpyAsync(out_groups, g.groups, n_rows * 4, hipMemcpyDeviceToHost, st));
+        RS_HIP(ctx, hipMemcpyAsync(out_buried, g.buried, n_rows * 4, hipMemcpyDeviceToHost, st));
+        RS_HIP(ctx, hipMemcpyAsync(out_only, g.only, n_rows * 4, hipMemcpyDeviceToHost, st));
+    }
+    RS_HIP(ctx, hipMemcpyAsync(out_self_free, g.self_free, N * 4, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipMemcpyAsync(out_free, g.free, N * 4, hipMemcpyDeviceToHost, st));
+    if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, g.p.sasa, N * 4, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+// ct_check, and the arrays every atom has an entry of.
+int gp_check(rsasa_context *ctx, size_t N, const float *x, const float *y, const float *z, const float *radius,
+             const uint32_t *group, size_t n_points, const uint64_t *out_offsets, const uint32_t *out_self_free,
+             const uint32_t *out_free)
+{
+    int rc;
+    if ((rc = ct_check(ctx, N, x, y, z, radius, n_points, out_offsets))) return rc;
+    if (N && (!group || !out_self_free || !out_free)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    return RSASA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -373,6 +464,39 @@ int rsasa_contact_points_batch(rsasa_context_t *ctx, const float *x, const float
     if ((rc = ct_check(ctx, N, x, y, z, radius, n_points, out_offsets))) return rc;
     return ct_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_offsets,
                   out_entries, out_covered, out_exclusive, entries_capacity, out_atom_sasa);
+}
+
+int rsasa_group_contacts(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                         const uint64_t *id, const uint32_t *group, size_t n_atoms, float probe_radius, size_t n_points,
+                         uint64_t *out_offsets, uint32_t *out_groups, uint32_t *out_buried, uint32_t *out_only,
+                         size_t rows_capacity, uint32_t *out_self_free, uint32_t *out_free, float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if ((rc = gp_check(ctx, n_atoms, x, y, z, radius, group, n_points, out_offsets, out_self_free, out_free))) return rc;
+    const uint32_t so[2] = {0u, (uint32_t)n_atoms};
+    return gp_run(ctx, x, y, z, radius, id, group, so, 1, n_atoms, probe_radius, n_points, out_offsets, out_groups, out_buried,
+                  out_only, rows_capacity, out_self_free, out_free, out_sasa);
+}
+
+int rsasa_group_contacts_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, const uint32_t *group, const uint32_t *structure_offsets,
+                               size_t n_structures, float probe_radius, size_t n_points, uint64_t *out_offsets,
+                               uint32_t *out_groups, uint32_t *out_buried, uint32_t *out_only, size_t rows_capacity,
+                               uint32_t *out_self_free, uint32_t *out_free, float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!structure_offsets) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_structures >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "too many structures");
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1])
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (n_structures && structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets[0] must be 0");
+    if ((rc = gp_check(ctx, N, x, y, z, radius, group, n_points, out_offsets, out_self_free, out_free))) return rc;
+    return gp_run(ctx, x, y, z, radius, id, group, structure_offsets, n_structures, N, probe_radius, n_points, out_offsets,
+                  out_groups, out_buried, out_only, rows_capacity, out_self_free, out_free, out_atom_sasa);
 }
 
 }  // extern "C"

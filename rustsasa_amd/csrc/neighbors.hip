@@ -353,6 +353,13 @@ void launch_neighbor_count(const NbArgs &a, hipStream_t stream)
     if (!n) return;
     if (a.b.sorted_id32) hipLaunchKernelGGL(k_neighbor_count<true>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(k_neighbor_count<false>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
+    launch_neighbor_scan(a, stream);
+}
+
+// offsets[] and NbInfo of counts[] that are already there (the group rows of rsasa_group_contacts* too)
+void launch_neighbor_scan(const NbArgs &a, hipStream_t stream)
+{
+    if (!a.b.n_atoms) return;
     hipLaunchKernelGGL(k_nb_scan_reduce, dim3(kNbScanBlocks), dim3(256), 0, stream, a);
     hipLaunchKernelGGL(k_nb_scan_parts, dim3(1), dim3(kNbScanBlocks), 0, stream, a);
     hipLaunchKernelGGL(k_nb_scan_apply, dim3(kNbScanBlocks), dim3(256), 0, stream, a);

@@ -9,6 +9,12 @@
 //                         two 32-bit words of the mask.
 //   k_contact_points      (rsasa_contact_points*) the same layout, no early exit: per entry of the list, the points it
 //                         hits (covered) and those it alone hits (exclusive), from two sweeps of the list per pass.
+//   k_group_order         (rsasa_group_contacts*) one wave per atom: its list again with the entries of its own group
+//                         (label) first and the others by (label, position), each entry ranked by counting the keys
+//                         below its own; the number of distinct foreign labels is the atom's row count.
+//   k_group_points        the layout of k_contact_points over the reordered list, one sweep per pass: the own-group
+//                         entries give `self`, every run of one foreign label an OR whose ballots are the row's buried
+//                         count; a point remembers the first row that hit it, which gives the rows' `only` counts.
 //
 // Points [0, n_fused) take the fused rule - mul_add(sx, vx, mul_add(sy, vy, sz * vz)) < limit (lib.rs:143-146) -, the
 // rest the remainder rule - plain products, `<=` (lib.rs:185-186,206-207).  Both rules are ORs over the list, so the
@@ -298,6 +304,269 @@ __global__ __launch_bounds__(256) void k_contact_points(CtArgs ct)
         a.sasa[row] = ((4.0f * 3.14159274101257324219f) * R2) * (float)exposed * (1.0f / (float)a.n_points);
 }
 
+// ---- group contacts (rsasa_group_contacts*) ----
+
+// The sort key of entry e (its position in the list, below 2^31) with label `lab` in the list of an atom labelled `mine`:
+// own-group entries first, then ascending unsigned label, then position.  No two entries of a list share a key.
+__device__ __forceinline__ unsigned long long gp_key(uint32_t lab, uint32_t mine, uint32_t e)
+{
+    const unsigned long long cls = lab == mine ? 0ull : (1ull << 32) | lab;
+    return (cls << 31) | e;
+}
+
+// One wave per cell-sorted atom.  Lane l takes entries l, l + 64, ... of the list; an entry's place in the new order is
+// the number of keys below its own, counted against the keys of the whole list, which pass through LDS kPtStage at a
+// time (any list length; K^2 / 64 steps per lane).  A foreign entry with no key of its label below it starts a row.
+__global__ __launch_bounds__(256) void k_group_order(GpArgs g)
+{
+    const PtArgs &a = g.p;
+    const BatchView &b = a.b;
+    __shared__ unsigned long long s_key[4][kPtStage];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t p = blockIdx.x * 4u + w;
+    if (p >= b.n_atoms) return;
+    const uint32_t row = b.sorted_orig[p];
+    const uint32_t base = b.grids[b.sid_sorted[p]].atom_begin;
+    const unsigned long long off = a.offsets[row];
+    const uint32_t K = (uint32_t)(a.offsets[row + 1] - off);
+    const uint2 *ent = a.entries + off;
+    const uint32_t mine = g.group[row];
+    const bool one_stage = K <= kPtStage;
+    uint32_t n_own = 0, n_rows = 0;
+    for (uint32_t eb = 0; eb < K; eb += kWave) {
+        const uint32_t e = eb + lane;
+        const bool valid = e < K;
+        const uint2 en = valid ? ent[e] : make_uint2(0u, 0u);
+        const uint32_t lab = valid ? g.group[base + en.y] : mine;  // idx is the index within the structure
+        const unsigned long long first = gp_key(lab, mine, 0u), key = first | e;
+        uint32_t rank = 0, before_label = 0;
+        for (uint32_t t0 = 0; t0 < K; t0 += kPtStage) {
+            const uint32_t n = min(kPtStage, K - t0);
+            if (!one_stage || eb == 0) {
+                wave_lds_fence();  // (every lane is done with the previous keys)
+                for (uint32_t k = lane; k < n; k += kWave) s_key[w][k] = gp_key(g.group[base + ent[t0 + k].y], mine, t0 + k);
+                wave_lds_fence();
+            }
+            for (uint32_t k = 0; k < n; k++) {
+                const unsigned long long o = s_key[w][k];  // (the same address in every lane: a broadcast)
+                rank += o < key ? 1u : 0u;
+                before_label += o < first ? 1u : 0u;
+            }
+        }
+        const bool own = valid && lab == mine;
+        n_own += (uint32_t)__popcll(ballot64(own));
+        n_rows += (uint32_t)__popcll(ballot64(valid && !own && rank == before_label));
+        if (valid) {
+            g.sorted[off + rank] = en;
+            g.sorted_group[off + rank] = lab;
+        }
+    }
+    if (lane == 0) {
+        g.n_own[row] = n_own;
+        g.n_rows[row] = n_rows;
+    }
+}
+
+constexpr uint32_t kGpOwn = 0, kGpInRun = 1, kGpRunEnd = 2;  // a staged entry: of the atom's own group / foreign / the last of its label
+constexpr uint32_t kGpRowRegs = 4;  // rows [0, 64 kGpRowRegs) of an atom are counted in registers: row r in lane r % 64
+
+// Entries [s0, s0 + n) of the reordered list -> s_run as (kind, label), padded like pt_stage's to a multiple of 4 with
+// foreign entries inside a run (they hit nothing).
+__device__ __forceinline__ void gp_stage_runs(const uint32_t *lab, uint32_t s0, uint32_t n, uint32_t K, uint32_t n_own,
+                                              uint2 *s_run)
+{
+    const uint32_t n4 = (n + 3u) & ~3u;
+    for (uint32_t e = lane_id(); e < n4; e += kWave) {
+        uint2 v = make_uint2(kGpInRun, 0u);
+        if (e < n) {
+            const uint32_t q = s0 + e, l = lab[q];
+            const bool last = q + 1u == K || lab[q + 1u] != l;
+            v = make_uint2(q < n_own ? kGpOwn : last ? kGpRunEnd : kGpInRun, l);
+        }
+        s_run[e] = v;
+    }
+}
+
+// Row r of the atom gains `cnt` (the same in every lane): in acc, lane r % 64's register r / 64; behind those registers
+// in dst[r] itself, which lane 0 alone writes and adds to (`add`: an earlier pass has written it).
+__device__ __forceinline__ void gp_row_add(uint32_t (&acc)[kGpRowRegs], uint32_t *dst, uint32_t r, uint32_t cnt, bool add)
+{
+    const uint32_t lane = lane_id();
+    if (r < kGpRowRegs * kWave) {
+        const bool mine = lane == (r & (kWave - 1u));
+#pragma unroll
+        for (uint32_t j = 0; j < kGpRowRegs; j++) acc[j] += mine && j == r / kWave ? cnt : 0u;
+    } else if (lane == 0) {
+        dst[r] = cnt + (add ? dst[r] : 0u);
+    }
+}
+
+struct GpRows {  // the rows of one atom
+    uint32_t *groups, *buried, *only;
+    uint32_t n;
+};
+
+// Staged entries [0, n) (n a multiple of 4) of the reordered list against the NCH chunks of a pass, with the tests of
+// pt_test.  An own-group entry's hits go to self; a foreign entry's hits on live points that self has left free go to
+// cov, and the last entry of a label closes row r: cov's ballots are its buried count, and every point keeps whether
+// one row or more than one has hit it and which row was the first.
+template <int NCH, bool REM>
+__device__ __forceinline__ void gp_test(const float4 *s_ent, const uint2 *s_run, uint32_t n, const float (&sx)[NCH],
+                                        const float (&sy)[NCH], const float (&sz)[NCH], const bool (&rem)[NCH],
+                                        const bool (&live)[NCH], bool (&self)[NCH], bool (&cov)[NCH], bool (&once)[NCH],
+                                        bool (&twice)[NCH], uint32_t (&first_row)[NCH], uint32_t &r,
+                                        uint32_t (&acc)[kGpRowRegs], const GpRows &rows, bool first_pass)
+{
+    for (uint32_t k = 0; k < n; k += 4) {
+        float4 e[4];
+        uint2 run[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) { e[u] = s_ent[k + u]; run[u] = s_run[k + u]; }
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            // (the same in every lane: a branch of the wave)
+            const uint32_t kind = (uint32_t)__builtin_amdgcn_readfirstlane((int)run[u].x);
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                bool hit = __builtin_fmaf(sx[c], e[u].x, __builtin_fmaf(sy[c], e[u].y, sz[c] * e[u].z)) < e[u].w;
+                if (REM) {
+                    const float dotu = sx[c] * e[u].x + sy[c] * e[u].y + sz[c] * e[u].z;
+                    hit = rem[c] ? dotu <= e[u].w : hit;
+                }
+                // (both updates, masked by the kind: a choice between two destinations would put them in scratch)
+                self[c] = self[c] || (hit && kind == kGpOwn);
+                cov[c] = cov[c] || (hit && kind != kGpOwn && live[c] && !self[c]);
+            }
+            if (kind == kGpRunEnd) {
+                uint32_t cnt = 0;
+#pragma unroll
+                for (int c = 0; c < NCH; c++) {
+                    cnt += (uint32_t)__popcll(ballot64(cov[c]));
+                    twice[c] = twice[c] || (once[c] && cov[c]);
+                    first_row[c] = cov[c] && !once[c] ? r : first_row[c];
+                    once[c] = once[c] || cov[c];
+                    cov[c] = false;
+                }
+                gp_row_add(acc, rows.buried, r, cnt, !first_pass);
+                if (first_pass && lane_id() == 0) rows.groups[r] = run[u].y;
+                r++;
+            }
+        }
+    }
+}
+
+// The layout of k_contact_points over the list k_group_order left (own group first, then one run per foreign label, so
+// the rows come out in ascending label order), one sweep per pass and no early exit.  After the sweep of a pass a
+// point hit by exactly one row belongs to that row's `only` count.
+template <int NCH>
+__global__ __launch_bounds__(256) void k_group_points(GpArgs g)
+{
+    const PtArgs &a = g.p;
+    const BatchView &b = a.b;
+    __shared__ float4 s_ent[4][kPtStage];
+    __shared__ uint2 s_run[4][kPtStage];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t p = blockIdx.x * 4u + w;
+    if (p >= b.n_atoms) return;
+    const uint32_t row = b.sorted_orig[p];
+    const uint32_t base = b.grids[b.sid_sorted[p]].atom_begin;
+    const float4 me = make_float4(b.x[row], b.y[row], b.z[row], b.radius[row]);
+    const float R = me.w + b.probe;  // lib.rs:101
+    const float R2 = R * R;          // lib.rs:102
+    const float twoR = 2.0f * R;     // lib.rs:136
+    const unsigned long long off = a.offsets[row];
+    const uint32_t K = (uint32_t)(a.offsets[row + 1] - off);
+    const uint2 *ent = g.sorted + off;
+    const uint32_t *lab = g.sorted_group + off;
+    const uint32_t n_own = g.n_own[row];
+    const unsigned long long r0 = g.row_offsets[row];
+    const GpRows rows = {g.groups + r0, g.buried + r0, g.only + r0, (uint32_t)(g.row_offsets[row + 1] - r0)};
+    const bool one_stage = K <= kPtStage;
+    if (one_stage && K) {
+        pt_stage(a, ent, 0, K, base, me, R2, twoR, s_ent[w]);
+        gp_stage_runs(lab, 0, K, K, n_own, s_run[w]);
+        wave_lds_fence();
+    }
+
+    // an empty list: no rows, every point free
+    const uint32_t n_chunks = K ? (a.n_points + kWave - 1) / kWave : 0u;
+    float nx[NCH], ny[NCH], nz[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const uint32_t pi = (uint32_t)c * kWave + lane;
+        const bool in = (uint32_t)c < n_chunks;
+        nx[c] = in ? a.lx[pi] : 0.0f;
+        ny[c] = in ? a.ly[pi] : 0.0f;
+        nz[c] = in ? a.lz[pi] : 0.0f;
+    }
+    uint32_t self_free = K ? 0u : a.n_points, exposed = self_free;
+    uint32_t acc_b[kGpRowRegs], acc_o[kGpRowRegs];
+#pragma unroll
+    for (uint32_t j = 0; j < kGpRowRegs; j++) acc_b[j] = acc_o[j] = 0u;
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += NCH) {
+        float sx[NCH], sy[NCH], sz[NCH];
+        bool live[NCH], rem[NCH], self[NCH], cov[NCH], once[NCH], twice[NCH];
+        uint32_t first_row[NCH];
+        bool any_rem = false;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            sx[c] = nx[c]; sy[c] = ny[c]; sz[c] = nz[c];
+            const uint32_t pi = (c0 + c) * kWave + lane;
+            live[c] = pi < a.n_points;  // lanes past the last point (and chunks past the last): never counted
+            rem[c] = pi >= a.n_fused;
+            any_rem = any_rem || (rem[c] && live[c]);
+            self[c] = cov[c] = once[c] = twice[c] = false;
+            first_row[c] = 0u;
+            const uint32_t nc = c0 + NCH + c;
+            const bool in = nc < n_chunks;
+            nx[c] = in ? a.lx[nc * kWave + lane] : 0.0f;
+            ny[c] = in ? a.ly[nc * kWave + lane] : 0.0f;
+            nz[c] = in ? a.lz[nc * kWave + lane] : 0.0f;
+        }
+        any_rem = ballot64(any_rem) != 0ull;
+        uint32_t r = 0;
+        for (uint32_t s0 = 0; s0 < K; s0 += kPtStage) {
+            const uint32_t n = min(kPtStage, K - s0);
+            if (!one_stage) {
+                wave_lds_fence();  // (every lane is done with the previous stage)
+                pt_stage(a, ent, s0, n, base, me, R2, twoR, s_ent[w]);
+                gp_stage_runs(lab, s0, n, K, n_own, s_run[w]);
+                wave_lds_fence();
+            }
+            const uint32_t n4 = (n + 3u) & ~3u;
+            if (any_rem) gp_test<NCH, true>(s_ent[w], s_run[w], n4, sx, sy, sz, rem, live, self, cov, once, twice, first_row, r,
+                                            acc_b, rows, c0 == 0);
+            else gp_test<NCH, false>(s_ent[w], s_run[w], n4, sx, sy, sz, rem, live, self, cov, once, twice, first_row, r,
+                                     acc_b, rows, c0 == 0);
+        }
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            self_free += (uint32_t)__popcll(ballot64(live[c] && !self[c]));
+            exposed += (uint32_t)__popcll(ballot64(live[c] && !self[c] && !once[c]));
+        }
+        for (uint32_t rr = 0; rr < rows.n; rr++) {
+            uint32_t cnt = 0;
+#pragma unroll
+            for (int c = 0; c < NCH; c++) cnt += (uint32_t)__popcll(ballot64(once[c] && !twice[c] && first_row[c] == rr));
+            gp_row_add(acc_o, rows.only, rr, cnt, c0 != 0);
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kGpRowRegs; j++) {
+        const uint32_t rr = j * kWave + lane;
+        if (rr < rows.n) {
+            rows.buried[rr] = acc_b[j];
+            rows.only[rr] = acc_o[j];
+        }
+    }
+    if (lane == 0) {
+        g.self_free[row] = self_free;
+        g.free[row] = exposed;
+        if (a.sasa)  // lib.rs:220-222, as k_accessible_points
+            a.sasa[row] = ((4.0f * 3.14159274101257324219f) * R2) * (float)exposed * (1.0f / (float)a.n_points);
+    }
+}
+
 }  // namespace
 
 // masks[] (and sasa[], if set) of every atom of the binned batch
@@ -316,6 +585,23 @@ void launch_contact_points(const CtArgs &c, hipStream_t stream)
     if (!n) return;
     if (c.p.n_points <= 2u * kWave) hipLaunchKernelGGL(k_contact_points<2>, dim3(cdiv(n, 4)), dim3(256), 0, stream, c);
     else hipLaunchKernelGGL(k_contact_points<4>, dim3(cdiv(n, 4)), dim3(256), 0, stream, c);
+}
+
+// sorted[], sorted_group[], n_own[] and n_rows[] of every atom of the binned batch
+void launch_group_order(const GpArgs &g, hipStream_t stream)
+{
+    const uint32_t n = g.p.b.n_atoms;
+    if (!n) return;
+    hipLaunchKernelGGL(k_group_order, dim3(cdiv(n, 4)), dim3(256), 0, stream, g);
+}
+
+// groups[], buried[] and only[] of every row, self_free[] and free[] (and p.sasa[], if set) of every atom
+void launch_group_points(const GpArgs &g, hipStream_t stream)
+{
+    const uint32_t n = g.p.b.n_atoms;
+    if (!n) return;
+    if (g.p.n_points <= 2u * kWave) hipLaunchKernelGGL(k_group_points<2>, dim3(cdiv(n, 4)), dim3(256), 0, stream, g);
+    else hipLaunchKernelGGL(k_group_points<4>, dim3(cdiv(n, 4)), dim3(256), 0, stream, g);
 }
 
 }  // namespace rsasa

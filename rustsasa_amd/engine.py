@@ -55,6 +55,19 @@ def _offsets(name, off):
     return off
 
 
+def _labels(groups, n):
+    """Group labels as a contiguous uint32 array of n entries: integers in [0, 2^32) only (a float or a negative label
+    would be another label after conversion)."""
+    g = np.asarray(groups)
+    if g.dtype.kind not in "ui":
+        raise ValueError(f"groups must be an array of integer labels (uint32), not {g.dtype}")
+    if g.ndim != 1 or g.shape[0] != n:
+        raise ValueError(f"groups must be a 1-D array of {n} entries (one label per atom)")
+    if g.dtype != np.uint32 and g.size and (int(g.min()) < 0 or int(g.max()) > 0xFFFFFFFF):
+        raise ValueError("group labels must lie in [0, 2^32)")
+    return np.ascontiguousarray(g, dtype=np.uint32)
+
+
 def _out_buffer(name, buf, n):
     """A caller-provided output array (e.g. pinned host memory) or a fresh one."""
     if buf is None:
@@ -322,6 +335,59 @@ class Context:
                 ptr(offsets), ptr(entries), ptr(covered), ptr(exclusive), cap, ptr(sasa))
         return self._contact_call(call, x.shape[0]) + (sasa,)
 
+    # ---- group contacts (which partner group buries which points: unions of the same tests over a label's entries) ----
+    def _group_call(self, call, n_atoms: int):
+        """The size-then-fill pattern of _contact_call for rows: call(offsets, groups, buried, only, capacity) with a
+        guessed capacity, and once more at offsets[-1] rows when that was too small; returns (offsets uint64[N + 1],
+        partner_groups uint32[rows], buried uint32[rows], only uint32[rows])."""
+        offsets = np.zeros(n_atoms + 1, np.uint64)
+        cols = [np.empty(16 * n_atoms, np.uint32) for _ in range(3)]
+        rc = call(offsets, *cols, cols[0].shape[0])
+        if rc == _capi.RSASA_ERR_BUFFER_TOO_SMALL:
+            cols = [np.empty(int(offsets[-1]), np.uint32) for _ in range(3)]
+            rc = call(offsets, *cols, cols[0].shape[0])
+        self._check(rc)
+        rows = int(offsets[-1])
+        return (offsets,) + tuple(c[:rows] for c in cols)
+
+    def group_contacts(self, x, y, z, radius, ids, groups, probe_radius: float = 1.4, n_points: int = 100):
+        """rsasa_group_contacts: (offsets uint64[N + 1], partner_groups uint32[rows], buried uint32[rows],
+        only uint32[rows], self_free uint32[N], free uint32[N], sasa float32[N]).  groups: a uint32 label per atom
+        (chain, residue, ligand).  Atom i has one row per distinct foreign label in its neighbour list, ascending:
+        buried = the points of sphere_points(n_points) on atom i that the label's atoms occlude among those atom i's own
+        group leaves free (self_free of them), only = those no other foreign label occludes; free = the accessible
+        points in the whole structure, sasa equals calculate_sasa_soa.  group_areas() sums rows into a group x group
+        table of A^2."""
+        n_points = _n_points(n_points)
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        groups = _labels(groups, x.shape[0])
+        self_free, free = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, partner, buried, only, cap):
+            return self._lib.rsasa_group_contacts(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(groups), x.shape[0], probe_radius, n_points,
+                ptr(offsets), ptr(partner), ptr(buried), ptr(only), cap, ptr(self_free), ptr(free), ptr(sasa))
+        return self._group_call(call, x.shape[0]) + (self_free, free, sasa)
+
+    def group_contacts_batch(self, x, y, z, radius, ids, groups, structure_offsets, probe_radius: float = 1.4,
+                             n_points: int = 100):
+        """rsasa_group_contacts_batch: group_contacts of every structure (one grid each), offsets over the whole batch;
+        labels are compared within a structure only, so their values may be reused from one structure to the next."""
+        n_points = _n_points(n_points)
+        so = _offsets("structure_offsets", structure_offsets)
+        n_struct = so.shape[0] - 1
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
+        groups = _labels(groups, x.shape[0])
+        self_free, free = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, partner, buried, only, cap):
+            return self._lib.rsasa_group_contacts_batch(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(groups), ptr(so), n_struct, probe_radius,
+                n_points, ptr(offsets), ptr(partner), ptr(buried), ptr(only), cap, ptr(self_free), ptr(free), ptr(sasa))
+        return self._group_call(call, x.shape[0]) + (self_free, free, sasa)
+
     def surface_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
         """The accessible points themselves: (atom_index uint32[M], xyz float32[M, 3]), see surface_points()."""
         words, _ = self.accessible_points(x, y, z, radius, ids, probe_radius, n_points)
@@ -489,6 +555,24 @@ def contact_areas(counts, offsets, radius, probe_radius: float = 1.4, n_points: 
             (np.float32(1.0) / np.float32(n_points))
 
 
+def group_areas(offsets, partner_groups, counts, groups, radius, probe_radius: float = 1.4, n_points: int = 100):
+    """Rows of group_contacts (buried or only) summed into a group x group table: (from_group uint32[P],
+    to_group uint32[P], area float64[P]), one entry per distinct ordered pair that has a row, sorted by (from, to).
+    area is the area of the atoms labelled `from` that group `to` takes: every row's area by contact_areas' float32
+    expression (R of the atom that owns the row), summed in float64.  (A, B) and (B, A) are separate entries - the area
+    of A buried by B and the area of B buried by A - and differ in general.  Labels are taken at face value: give a
+    batch structure by structure unless its structures use different labels."""
+    area = contact_areas(counts, offsets, radius, probe_radius, n_points)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    groups = _labels(groups, offsets.shape[0] - 1)
+    partner = _labels(partner_groups, area.shape[0])
+    owner = np.repeat(groups, np.diff(offsets.astype(np.int64)))
+    key = (owner.astype(np.uint64) << np.uint64(32)) | partner.astype(np.uint64)
+    pairs, inverse = np.unique(key, return_inverse=True)
+    total = np.bincount(inverse.reshape(-1), weights=area.astype(np.float64), minlength=pairs.shape[0])
+    return (pairs >> np.uint64(32)).astype(np.uint32), (pairs & np.uint64(0xFFFFFFFF)).astype(np.uint32), total
+
+
 def make_atoms(x, y, z, radius, ids) -> np.ndarray:
     """Packs SoA columns into rsasa_atom_t records."""
     a = np.zeros(len(x), ATOM_DTYPE)
@@ -501,4 +585,4 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 
 
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
-           "contact_areas", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
+           "contact_areas", "group_areas", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
