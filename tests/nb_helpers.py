@@ -136,3 +136,27 @@ def tight_cluster(n, seed, protein="1jcd.pdb", shared_ids=False):
     cr = rng.uniform(1.2, 1.9, n).astype(np.float32)
     cat = lambda a, b: np.ascontiguousarray(np.concatenate([a, b]))  # noqa: E731
     return (cat(x, c[:, 0]), cat(y, c[:, 1]), cat(z, c[:, 2]), cat(r, cr), cat(ids, cid)), len(x)
+
+
+SCAN_BLOCKS = 1024  # k_nb_scan_*: 1 024 blocks, chunks of a multiple of 256 counts
+
+
+def scan_chunk(n):
+    """Counts per scan block for n atoms (nb_scan_range)."""
+    chunk = (n + SCAN_BLOCKS - 1) // SCAN_BLOCKS
+    return (chunk + 255) // 256 * 256
+
+
+def scan_input(n, kind):
+    """n atoms: one jittered lattice (single) or a proteome-like batch cut to exactly n atoms."""
+    if kind == "single":
+        b = bw.synthetic_uniform(n, seed=n % 997)
+        return b.x, b.y, b.z, b.radius, b.ids, np.array([0, n], np.uint32)
+    b = bw.synthetic_proteome(200, seed=6)
+    reps = -(-n // b.n_atoms)
+    so = [0]
+    for _ in range(reps):
+        so += [int(o) + so[-1] for o in b.structure_offsets[1:]]
+    so = np.array([o for o in so if o < n] + [n], np.uint32)
+    tile = lambda a: np.ascontiguousarray(np.tile(a, reps)[:n])  # noqa: E731
+    return tile(b.x), tile(b.y), tile(b.z), tile(b.radius), tile(b.ids), so

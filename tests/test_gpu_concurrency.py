@@ -544,3 +544,113 @@ def test_call_combining_opens_a_second_block_when_one_is_full():
     b1, c1 = rustsasa_amd.Context.call_combining_stats(0)
     assert errors == []
     assert c1 - c0 == 14 * 6 and b1 - b0 >= (14 * 6 * 30_000) // 196_608  # (no block held more than it can)
+
+
+# ---- the list, point, contact and group calls from several host threads -------------------------------------------
+
+MIXED_POINTS = (100, 130, 64)   # rotated, so the lattice a context caches changes under its lock
+MIXED_CALLS = ("group_contacts", "contact_points", "accessible_points", "precompute_neighbors", "calculate_sasa_soa")
+MIXED_W = 8
+_MIXED = []
+
+
+def _mixed_cases():
+    """[(columns, labels, {n_points: expected results})] on the four small fixtures, every expectation from the CPU
+    models and the oracle, computed before any thread starts."""
+    import groups_model as gm
+    import nb_helpers as nh
+    import point_edge_cases as pe
+    import points_model as pm
+    if _MIXED:
+        return _MIXED
+    cols = [nh.protor(name) for name in ("1jcd.pdb", "151L_H3.pdb", "bad_seqadv_1A06.pdb", "example.cif")]
+    labels = [np.arange(len(c[0]), dtype=np.uint32) // np.uint32(40) for c in cols]
+    keys = [(k, n) for k in range(len(cols)) for n in MIXED_POINTS]
+
+    def one(key):
+        k, n = key
+        offs, ent, by_w = pe.models(cols[k], PROBE, n, (MIXED_W,))
+        mask, cov, exc, _ = by_w[MIXED_W]
+        return {"lists": (offs, ent), "words": pm.pack(mask), "covered": cov, "exclusive": exc,
+                "groups": gm.group_counts(*cols[k], labels[k], PROBE, n, MIXED_W, lists=(offs, ent)),
+                "sasa": po.calculate_sasa_internal(*cols[k], PROBE, n, MIXED_W)}
+    done = pe.pmap(one, keys)
+    _MIXED.extend((cols[k], labels[k], {n: done[(k, n)] for n in MIXED_POINTS}) for k in range(len(cols)))
+    return _MIXED
+
+
+def _mixed_call(c, call, cols, g, n_points, want):
+    """One call of the rotation against its expectation: a description of the first difference, or None."""
+    same = lambda a, b: a.shape == b.shape and a.tobytes() == b.tobytes()  # noqa: E731
+    if call == "group_contacts":
+        got = c.group_contacts(*cols, g, PROBE, n_points)
+        bad = [k for k in range(6) if not np.array_equal(got[k], want["groups"][k])]
+        return bad or (None if same(got[6], want["sasa"]) else "sasa")
+    if call == "contact_points":
+        offs, ent, cov, exc, sasa = c.contact_points(*cols, PROBE, n_points)
+        ok = np.array_equal(offs, want["lists"][0]) and same(ent, want["lists"][1]) and np.array_equal(cov, want["covered"]) \
+            and np.array_equal(exc, want["exclusive"]) and same(sasa, want["sasa"])
+        return None if ok else "differs"
+    if call == "accessible_points":
+        words, sasa = c.accessible_points(*cols, PROBE, n_points)
+        return None if np.array_equal(words, want["words"]) and same(sasa, want["sasa"]) else "differs"
+    if call == "precompute_neighbors":
+        offs, ent = c.precompute_neighbors(*cols, PROBE)
+        return None if np.array_equal(offs, want["lists"][0]) and same(ent, want["lists"][1]) else "differs"
+    got = c.calculate_sasa_soa(*cols, PROBE, n_points)
+    return None if same(got, want["sasa"]) else "differs"
+
+
+def _hammer_mixed(contexts, cases, rounds):
+    """Eight threads, each rotating through the five calls, the four fixtures and the three point counts."""
+    errors = []
+
+    def work(tid):
+        try:
+            c = contexts[tid % len(contexts)]
+            for it in range(rounds):
+                call = MIXED_CALLS[(tid + it) % len(MIXED_CALLS)]
+                cols, g, by_points = cases[(tid // 2 + it) % len(cases)]
+                n_points = MIXED_POINTS[(tid + 2 * it) % len(MIXED_POINTS)]
+                bad = _mixed_call(c, call, cols, g, n_points, by_points[n_points])
+                if bad:
+                    errors.append((tid, it, call, n_points, bad))
+        except Exception as e:  # noqa: BLE001
+            errors.append((tid, repr(e)))
+
+    threads = [threading.Thread(target=work, args=(t,)) for t in range(8)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    return errors
+
+
+def test_rotation_covers_every_call_fixture_and_point_count():
+    seen = {(MIXED_CALLS[(t + i) % 5], (t // 2 + i) % 4, MIXED_POINTS[(t + 2 * i) % 3]) for t in range(8) for i in range(10)}
+    assert {s[0] for s in seen} == set(MIXED_CALLS) and {s[1] for s in seen} == {0, 1, 2, 3}
+    assert {(s[0], s[2]) for s in seen} == {(c, n) for c in MIXED_CALLS for n in MIXED_POINTS}
+    assert {s[:2] for s in seen} == {(c, k) for c in MIXED_CALLS for k in range(4)}
+
+
+def test_list_point_contact_and_group_calls_share_one_context():
+    """precompute_neighbors, accessible_points, contact_points and group_contacts keep their lists, lattice and rows in
+    the context (nb_*, pt_*, ct_*, gp_*): eight threads on one context, every result against its model."""
+    import rustsasa_amd
+    cases = _mixed_cases()
+    with rustsasa_amd.Context(0) as c:
+        c.set_simd_width(MIXED_W)
+        assert _hammer_mixed([c], cases, 10) == []
+
+
+def test_list_point_contact_and_group_calls_one_context_per_thread():
+    import rustsasa_amd
+    cases = _mixed_cases()
+    contexts = [rustsasa_amd.Context(0) for _ in range(8)]
+    try:
+        for c in contexts:
+            c.set_simd_width(MIXED_W)
+        assert _hammer_mixed(contexts, cases, 10) == []
+    finally:
+        for c in contexts:
+            c.close()

@@ -18,13 +18,12 @@ import bench_workloads as bw
 import neighbor_model as nm
 import tie_cases as tc
 from nb_helpers import (PROBE, assert_same, check_invariants, fold_max, oracle_active_csr, oracle_batch_csr,
-                        oracle_csr, protor, tight_cluster)
+                        oracle_csr, protor, scan_chunk, scan_input, tight_cluster)
 
 pytestmark = pytest.mark.gpu
 
 NB_STAGE = 512  # keys one wave stages in LDS in k_neighbor_fill (kNbStage, neighbors.hip); longer lists spill
 SPILL_GRID = 4096  # k_neighbor_rank_spill's grid is capped at 4 096 workgroups, one list each per round
-SCAN_BLOCKS = 1024  # k_nb_scan_*: 1 024 blocks, chunks of a multiple of 256 counts
 
 
 @pytest.fixture(scope="module")
@@ -120,28 +119,14 @@ def test_real_structure_with_lists_on_both_sides_of_the_staging(ctx):
 
 # ---- 2. the count scan's chunks ---------------------------------------------------------------------------------
 
-def _scan_input(n, kind):
-    """n atoms: one jittered lattice (single) or a proteome-like batch cut to exactly n atoms."""
-    if kind == "single":
-        b = bw.synthetic_uniform(n, seed=n % 997)
-        return b.x, b.y, b.z, b.radius, b.ids, np.array([0, n], np.uint32)
-    b = bw.synthetic_proteome(200, seed=6)
-    reps = -(-n // b.n_atoms)
-    so = [0]
-    for _ in range(reps):
-        so += [int(o) + so[-1] for o in b.structure_offsets[1:]]
-    so = np.array([o for o in so if o < n] + [n], np.uint32)
-    tile = lambda a: np.ascontiguousarray(np.tile(a, reps)[:n])  # noqa: E731
-    return tile(b.x), tile(b.y), tile(b.z), tile(b.radius), tile(b.ids), so
+_scan_input = scan_input
 
 
 SCAN_SIZES = [262144, 262145, 524289]
 SCAN_PROBE = 0.0  # (short lists: the scan, not the lists, is under test here)
 
 
-def _chunk(n):
-    chunk = (n + SCAN_BLOCKS - 1) // SCAN_BLOCKS
-    return (chunk + 255) // 256 * 256  # (nb_scan_range)
+_chunk = scan_chunk
 
 
 @pytest.mark.parametrize("kind", ["single", "batch"])
