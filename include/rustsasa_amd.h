@@ -38,7 +38,7 @@ extern "C" {
  * Additive under 4 (callers detect them by symbol): rsasa_neighbor_t, rsasa_precompute_neighbors,
  * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL; rsasa_accessible_points,
  * rsasa_accessible_points_batch; rsasa_contact_points, rsasa_contact_points_batch; rsasa_group_contacts,
- * rsasa_group_contacts_batch. */
+ * rsasa_group_contacts_batch; rsasa_exposure_vectors, rsasa_exposure_vectors_batch, rsasa_sas_volume. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -410,6 +410,98 @@ int rsasa_accessible_points_batch(rsasa_context_t *ctx,
                                   const uint32_t *structure_offsets, size_t n_structures,
                                   float probe_radius, size_t n_points,
                                   uint32_t *out_masks, float *out_atom_sasa);
+
+/* ---- exposure vectors --------------------------------------------------- */
+
+/* IN WHICH DIRECTION an atom is exposed, and the volume the accessible
+ * surface encloses: per atom the vector sum of its exposed lattice points
+ *
+ *     E_i = sum over the exposed points p of s_p,
+ *
+ * s_p the unit lattice points of rsasa_sphere_points, exposed as
+ * rsasa_accessible_points decides it (the same lists, the same two rules, W
+ * the context's lane count).  E_i / k_i is the atom's mean outward direction
+ * (summed over a residue: the side it is exposed on, as half-sphere-exposure
+ * style descriptors need it); with the counts k_i the sums give the volume
+ * inside the dot surface (rsasa_sas_volume below).
+ *
+ *   out_vectors[3 i + {0, 1, 2}] = E_i (x, y, z), float32;
+ *   out_free[i]                  = k_i, the exposed count: the popcount of
+ *                                  rsasa_accessible_points;
+ *   out_sasa[i]                  (nullable) bit for bit
+ *                                  rsasa_calculate_sasa_batch.
+ *
+ * The float32 summation order is part of the interface, so results can be
+ * checked bit for bit.  The lattice is taken in chunks of 64 points (zero
+ * padded); the term of a point is t = occluded ? +0.0f : s for each of the
+ * three components, and the lanes past n_points are occluded.
+ *   1. Within a chunk, with lanes l = 0..63: for h = 32, 16, 8, 4, 2, 1, set
+ *      t[l] = t[l] + t[l + h] for l < h.  The chunk's sum is t[0].
+ *   2. Across chunks, ascending c: E = chunk_0, then E = E + chunk_c.
+ *   3. Only plain adds (no fused multiply-add, no reassociation).
+ * An atom with no exposed point has E = (+0.0f, +0.0f, +0.0f).
+ *
+ * Non-finite input as rsasa_accessible_points: an atom with a NaN coordinate
+ * or a NaN radius gets the full lattice sum (every point a term) and
+ * out_free = n_points (its out_sasa is NaN for a NaN radius); an infinite
+ * coordinate returns RSASA_ERR_GRID_TOO_LARGE and the context stays usable.
+ * The argument errors are those of rsasa_accessible_points (n_points == 0,
+ * probe_radius + largest radius not a positive finite number,
+ * structure_offsets that are not non-decreasing from 0, NULL columns); in
+ * addition out_vectors or out_free NULL where there are atoms returns
+ * RSASA_ERR_INVALID_ARGUMENT.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight (rsasa_batch_enqueue) are neither waited
+ * for nor disturbed.  No masks are written or read anywhere: 16 bytes per atom
+ * cross the link (and 4 for out_sasa); the lists stay on the device. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).
+ * out_vectors: [n_atoms * 3]; out_free: [n_atoms]; out_sasa: [n_atoms] or
+ * NULL. */
+int rsasa_exposure_vectors(rsasa_context_t *ctx,
+                           const float *x, const float *y, const float *z, const float *radius,
+                           const uint64_t *id, size_t n_atoms,
+                           float probe_radius, size_t n_points,
+                           float *out_vectors, uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each).
+ * out_vectors: [structure_offsets[n_structures] * 3]; out_free and
+ * out_atom_sasa (nullable): [structure_offsets[n_structures]]. */
+int rsasa_exposure_vectors_batch(rsasa_context_t *ctx,
+                                 const float *x, const float *y, const float *z, const float *radius,
+                                 const uint64_t *id,
+                                 const uint32_t *structure_offsets, size_t n_structures,
+                                 float probe_radius, size_t n_points,
+                                 float *out_vectors, uint32_t *out_free, float *out_atom_sasa);
+
+/* The volume the dot surface encloses, per structure, from the vectors and
+ * counts above - the divergence theorem on the dots, the volume a
+ * double-cubic-lattice SASA tool reports beside its area:
+ *
+ *     V = sum_i (a_i / 3) (R_i k_i + (c_i - o) . E_i),   A = sum_i a_i k_i,
+ *
+ * a_i = 4 pi R_i^2 / n_points, R_i = (double)(radius_i + probe_radius) with the
+ * sum taken in float32 (the engine's R), k_i = free[i], c_i the centre, o the
+ * structure's origin: origins[3 s ..] or, origins NULL, the mean centre of
+ * the structure's counted atoms (accumulated in double in atom order).  V does
+ * not depend on o for a closed surface; on the dots the choice changes it
+ * within their discretisation error, and an origin inside the structure keeps
+ * that small.  A host utility: no context, no GPU; computed in double, in atom
+ * order.  Atoms with a non-finite coordinate or radius are skipped (no term,
+ * not counted in the mean centre), so the results stay finite.  An empty
+ * structure has volume 0 and area 0.
+ * x, y, z, radius, free: [structure_offsets[n_structures]]; vectors: three per
+ * atom; out_volume: [n_structures]; out_area: [n_structures] or NULL.
+ * structure_offsets NULL or not non-decreasing from 0, n_points == 0, or a
+ * NULL array where there are atoms (out_volume where there are structures)
+ * return RSASA_ERR_INVALID_ARGUMENT. */
+int rsasa_sas_volume(const float *x, const float *y, const float *z, const float *radius,
+                     const float *vectors, const uint32_t *free,
+                     const uint32_t *structure_offsets, size_t n_structures,
+                     float probe_radius, size_t n_points,
+                     const double *origins, double *out_volume, double *out_area);
 
 /* ---- contact counts ----------------------------------------------------- */
 

@@ -107,6 +107,12 @@ SYMBOLS = {
                                           _vp, _vp]),
     "rsasa_accessible_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,
                                                 C.c_size_t, _vp, _vp]),
+    "rsasa_exposure_vectors": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
+                                         _vp, _vp, _vp]),
+    "rsasa_exposure_vectors_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,
+                                               C.c_size_t, _vp, _vp, _vp]),
+    "rsasa_sas_volume": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
+                                   _vp, _vp, _vp]),
     "rsasa_contact_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsasa_contact_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,

@@ -214,6 +214,15 @@ struct PtArgs {
     float *sasa;                        // [n_atoms] or null: ((4 pi R^2) popcount) / n_points (lib.rs:220-222)
 };
 
+// ---- exposure vectors (points.hip, rsasa_exposure_vectors*) ----
+// The same lists and lattice (p.masks and p.words unused): per atom the sum of its exposed lattice points and their number.
+struct ExArgs {
+    PtArgs p;                           // p.sasa: [n_atoms] or null, ((4 pi R^2) k) / n_points with k = free
+    float *vectors;                     // [n_atoms][3], input order: the float32 sum of the exposed points of the unit lattice,
+                                        // a tree over the 64 lanes of a chunk, then the chunks ascending (k_exposure_vectors)
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of PtArgs::masks
+};
+
 // ---- contact counts (points.hip, rsasa_contact_points*) ----
 // The same lists and lattice (p.masks unused), per-entry counts out, aligned with NbArgs::out.
 struct CtArgs {
@@ -299,6 +308,8 @@ void launch_neighbor_count(const NbArgs &a, hipStream_t stream);
 void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
 // The point masks (points.hip) from those lists.
 void launch_accessible_points(const PtArgs &a, hipStream_t stream);
+// The exposed-point sums and counts (points.hip) from those lists.
+void launch_exposure_vectors(const ExArgs &e, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);
 // The 64-bit exclusive scan of the count pass by itself (neighbors.hip): a.counts -> a.offsets[0 .. n_atoms], totals -> a.info.

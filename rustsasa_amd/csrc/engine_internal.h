@@ -454,6 +454,8 @@ struct rsasa_context {
     // path's cached lattices reorder the points above 128)
     DeviceBuffer pt_masks, pt_sasa, pt_lattice;
     size_t pt_lattice_points = 0;  // the point count pt_lattice holds (0: none)
+    // rsasa_exposure_vectors*: the sums and counts of the last call (the lists, lattice and values are the buffers above)
+    DeviceBuffer ex_vectors, ex_free;
     // rsasa_contact_points*: the per-entry counts of the last call (the lists, lattice and values are the buffers above)
     DeviceBuffer ct_covered, ct_exclusive;
     // rsasa_group_contacts*: the labels, the lists in label order with their own-group and row counts, the row offsets,

@@ -1,9 +1,12 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h): the
 // batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws), then
 // neighbors.hip counts, scans and fills the lists.  The accessible-point entry points (rsasa_accessible_points /
-// _batch) run the same stages and hand the lists, still on the device, to points.hip; so do the contact counts
-// (rsasa_contact_points*) and the group contacts (rsasa_group_contacts*).  Host code only.
+// _batch) run the same stages and hand the lists, still on the device, to points.hip; so do the exposure vectors
+// (rsasa_exposure_vectors*), the contact counts (rsasa_contact_points*) and the group contacts (rsasa_group_contacts*).
+// rsasa_sas_volume is plain host arithmetic on what the exposure vectors return.  Host code only.
 #include "engine_internal.h"
+
+#include <cmath>
 
 namespace {
 
@@ -191,6 +194,48 @@ int pt_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     RS_HIP(ctx, hipGetLastError());
     RS_HIP(ctx, hipMemcpyAsync(out_masks, pa.masks, N * words * 4, hipMemcpyDeviceToHost, st));
     if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, pa.sasa, N * 4, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+// ---- exposure vectors (rsasa_exposure_vectors*) ----
+
+// One run of the exposure vectors: the lists of pt_run stay on the device and k_exposure_vectors turns them into the sum
+// of each atom's exposed lattice points and their number; 16 bytes per atom come back (and 4 for the value, if asked).
+int ex_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *so, size_t S, size_t N, float probe, size_t n_points, float *out_vectors, uint32_t *out_free,
+           float *out_sasa)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) return RSASA_OK;
+    size_t padded = 0;
+    if ((rc = pt_lattice(ctx, n_points, padded))) return rc;
+    NbArgs a{};
+    NbInfo info{};
+    if ((rc = nb_count(ctx, x, y, z, r, id, so, S, N, nullptr, probe, __builtin_nanf(""), nullptr, a, info))) return rc;
+    if (info.total && (rc = nb_fill(ctx, a, info))) return rc;
+    if ((rc = reserve(ctx, ctx->ex_vectors, N * 12)) || (rc = reserve(ctx, ctx->ex_free, N * 4)) ||
+        (out_sasa && (rc = reserve(ctx, ctx->pt_sasa, N * 4))))
+        return rc;
+    ExArgs e{};
+    e.p.b = a.b;
+    e.p.offsets = a.offsets;
+    e.p.entries = (const uint2 *)ctx->nb_entries.p;  // (not read when every list is empty)
+    const float *lat = (const float *)ctx->pt_lattice.p;
+    e.p.lx = lat; e.p.ly = lat + padded; e.p.lz = lat + 2 * padded;
+    e.p.n_points = (uint32_t)n_points;
+    e.p.n_fused = (uint32_t)(n_points - n_points % (size_t)ctx->simd_width);
+    e.p.sasa = out_sasa ? (float *)ctx->pt_sasa.p : nullptr;
+    e.vectors = (float *)ctx->ex_vectors.p;
+    e.free = (uint32_t *)ctx->ex_free.p;
+    hipStream_t st = ctx->stream;
+    launch_exposure_vectors(e, st);
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, hipMemcpyAsync(out_vectors, e.vectors, N * 12, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipMemcpyAsync(out_free, e.free, N * 4, hipMemcpyDeviceToHost, st));
+    if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, e.p.sasa, N * 4, hipMemcpyDeviceToHost, st));
     RS_HIP(ctx, hipStreamSynchronize(st));
     return RSASA_OK;
 }
@@ -431,6 +476,81 @@ int rsasa_accessible_points_batch(rsasa_context_t *ctx, const float *x, const fl
     if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
     if (N && (!x || !y || !z || !radius || !out_masks)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
     return pt_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_masks, out_atom_sasa);
+}
+
+int rsasa_exposure_vectors(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                           const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, float *out_vectors,
+                           uint32_t *out_free, float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (n_atoms && (!x || !y || !z || !radius || !out_vectors || !out_free)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
+    if (n_atoms >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    const uint32_t so[2] = {0u, (uint32_t)n_atoms};
+    return ex_run(ctx, x, y, z, radius, id, so, 1, n_atoms, probe_radius, n_points, out_vectors, out_free, out_sasa);
+}
+
+int rsasa_exposure_vectors_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                                 const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures,
+                                 float probe_radius, size_t n_points, float *out_vectors, uint32_t *out_free,
+                                 float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!structure_offsets) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
+    if (n_structures >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "too many structures");
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1])
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (n_structures && structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets[0] must be 0");
+    if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    if (N && (!x || !y || !z || !radius || !out_vectors || !out_free)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    return ex_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_vectors, out_free,
+                  out_atom_sasa);
+}
+
+// No context, no device: double arithmetic in atom order on the host.
+int rsasa_sas_volume(const float *x, const float *y, const float *z, const float *radius, const float *vectors,
+                     const uint32_t *free_points, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                     size_t n_points, const double *origins, double *out_volume, double *out_area)
+{
+    if (!structure_offsets || n_points == 0 || (n_structures && !out_volume)) return RSASA_ERR_INVALID_ARGUMENT;
+    if (n_structures && structure_offsets[0] != 0) return RSASA_ERR_INVALID_ARGUMENT;
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1]) return RSASA_ERR_INVALID_ARGUMENT;
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (N && (!x || !y || !z || !radius || !vectors || !free_points)) return RSASA_ERR_INVALID_ARGUMENT;
+    const double four_pi = 4.0 * 3.14159265358979323846;
+    for (size_t s = 0; s < n_structures; s++) {
+        const size_t b = structure_offsets[s], e = structure_offsets[s + 1];
+        auto counted = [&](size_t i) { return std::isfinite(x[i]) && std::isfinite(y[i]) && std::isfinite(z[i]) && std::isfinite(radius[i]); };
+        double ox = 0.0, oy = 0.0, oz = 0.0;
+        if (origins) {
+            ox = origins[3 * s]; oy = origins[3 * s + 1]; oz = origins[3 * s + 2];
+        } else {
+            size_t n = 0;
+            for (size_t i = b; i < e; i++)
+                if (counted(i)) { ox += (double)x[i]; oy += (double)y[i]; oz += (double)z[i]; n++; }
+            if (n) { ox /= (double)n; oy /= (double)n; oz /= (double)n; }
+        }
+        double vol = 0.0, area = 0.0;
+        for (size_t i = b; i < e; i++) {
+            if (!counted(i)) continue;
+            const float Rf = radius[i] + probe_radius;  // lib.rs:101, in float32
+            const double R = (double)Rf, k = (double)free_points[i];
+            const double a = (four_pi * (R * R)) / (double)n_points;
+            const double dot = ((double)x[i] - ox) * (double)vectors[3 * i] + ((double)y[i] - oy) * (double)vectors[3 * i + 1] +
+                               ((double)z[i] - oz) * (double)vectors[3 * i + 2];
+            vol += (a / 3.0) * (R * k + dot);
+            area += a * k;
+        }
+        out_volume[s] = vol;
+        if (out_area) out_area[s] = area;
+    }
+    return RSASA_OK;
 }
 
 int rsasa_contact_points(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,

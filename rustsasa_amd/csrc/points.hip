@@ -15,6 +15,9 @@
 //   k_group_points        the layout of k_contact_points over the reordered list, one sweep per pass: the own-group
 //                         entries give `self`, every run of one foreign label an OR whose ballots are the row's buried
 //                         count; a point remembers the first row that hit it, which gives the rows' `only` counts.
+//   k_exposure_vectors    (rsasa_exposure_vectors*) the layout, staging, tests and early exit of k_accessible_points; no
+//                         masks: per atom the float32 sum of its exposed lattice points, in a fixed order (a tree over
+//                         the lanes of a chunk, then the chunks ascending), and their number.
 //
 // Points [0, n_fused) take the fused rule - mul_add(sx, vx, mul_add(sy, vy, sz * vz)) < limit (lib.rs:143-146) -, the
 // rest the remainder rule - plain products, `<=` (lib.rs:185-186,206-207).  Both rules are ORs over the list, so the
@@ -567,6 +570,118 @@ __global__ __launch_bounds__(256) void k_group_points(GpArgs g)
     }
 }
 
+// ---- exposure vectors (rsasa_exposure_vectors*) ----
+
+// The sum of t over the chunk's 64 lanes in the interface's order: for h = 32, 16, 8, 4, 2, 1, t[l] = t[l] + t[l + h]
+// for l < h; the chunk's sum is t[0].  Lane l < h of the xor butterfly adds exactly t[l] + t[l + h] (the lanes above h
+// compute sums nobody reads), so lane 0 ends with that tree.  Plain float32 adds (-ffp-contract=off, no fast-math).
+__device__ __forceinline__ float ex_chunk_sum(float t)
+{
+#pragma unroll
+    for (int h = kWave / 2; h >= 1; h >>= 1) t = t + __shfl_xor(t, h, kWave);
+    return t;
+}
+
+// The layout of k_accessible_points (one wave per cell-sorted atom, lanes over NCH chunks of 64 points per pass, the list
+// staged by pt_stage and tested by pt_test with its early exit), no masks.  After a pass every lane holds occ[c] of its
+// point of chunk c; its term is occ ? +0.0f : s per component (the lattice is zero padded and the lanes past n_points
+// are occ).  A chunk sums its terms by ex_chunk_sum, the chunks are added in ascending order: E = chunk_0, then
+// E = E + chunk_c.  A chunk with no exposed lane has 64 terms +0.0f, whose tree is +0.0f: that is added without the
+// shuffles.  Lane 0 writes the three sums, the exposed count and the value.
+template <int NCH>
+__global__ __launch_bounds__(256) void k_exposure_vectors(ExArgs ex)
+{
+    const PtArgs &a = ex.p;
+    const BatchView &b = a.b;
+    __shared__ float4 s_ent[4][kPtStage];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t p = blockIdx.x * 4u + w;
+    if (p >= b.n_atoms) return;
+    const uint32_t row = b.sorted_orig[p];
+    const uint32_t base = b.grids[b.sid_sorted[p]].atom_begin;
+    const float4 me = make_float4(b.x[row], b.y[row], b.z[row], b.radius[row]);
+    const float R = me.w + b.probe;  // lib.rs:101
+    const float R2 = R * R;          // lib.rs:102
+    const float twoR = 2.0f * R;     // lib.rs:136
+    const unsigned long long off = a.offsets[row];
+    const uint32_t K = (uint32_t)(a.offsets[row + 1] - off);
+    const uint2 *ent = a.entries + off;
+    const bool one_stage = K <= kPtStage;
+    if (one_stage && K) {
+        pt_stage(a, ent, 0, K, base, me, R2, twoR, s_ent[w]);
+        wave_lds_fence();
+    }
+
+    const uint32_t n_chunks = (a.n_points + kWave - 1) / kWave;
+    // the points of the next pass are loaded while this one runs (the lattice arrays are zero padded to whole chunks)
+    float nx[NCH], ny[NCH], nz[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const uint32_t pi = (uint32_t)c * kWave + lane;
+        const bool in = (uint32_t)c < n_chunks;
+        nx[c] = in ? a.lx[pi] : 0.0f;
+        ny[c] = in ? a.ly[pi] : 0.0f;
+        nz[c] = in ? a.lz[pi] : 0.0f;
+    }
+    uint32_t exposed = 0;
+    float ex_x = 0.0f, ex_y = 0.0f, ex_z = 0.0f;  // (E = chunk_0 overwrites them)
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += NCH) {
+        float sx[NCH], sy[NCH], sz[NCH];
+        bool occ[NCH], rem[NCH];
+        bool any_rem = false;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            sx[c] = nx[c]; sy[c] = ny[c]; sz[c] = nz[c];
+            const uint32_t pi = (c0 + c) * kWave + lane;
+            occ[c] = pi >= a.n_points;  // lanes past the last point (and chunks past the last): never exposed
+            rem[c] = pi >= a.n_fused;
+            any_rem = any_rem || (rem[c] && !occ[c]);
+            const uint32_t nc = c0 + NCH + c;
+            const bool in = nc < n_chunks;
+            nx[c] = in ? a.lx[nc * kWave + lane] : 0.0f;
+            ny[c] = in ? a.ly[nc * kWave + lane] : 0.0f;
+            nz[c] = in ? a.lz[nc * kWave + lane] : 0.0f;
+        }
+        any_rem = ballot64(any_rem) != 0ull;
+        for (uint32_t s0 = 0; s0 < K; s0 += kPtStage) {
+            const uint32_t n = min(kPtStage, K - s0);
+            if (!one_stage) {
+                wave_lds_fence();  // (every lane is done with the previous stage)
+                pt_stage(a, ent, s0, n, base, me, R2, twoR, s_ent[w]);
+                wave_lds_fence();
+            }
+            const uint32_t n4 = (n + 3u) & ~3u;
+            if (any_rem ? pt_test<NCH, true>(s_ent[w], n4, sx, sy, sz, rem, occ)
+                        : pt_test<NCH, false>(s_ent[w], n4, sx, sy, sz, rem, occ))
+                break;
+        }
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            if (c0 + c >= n_chunks) break;  // (the same in every lane) the chunks past the last are no terms of the sum
+            const unsigned long long m = ballot64(!occ[c]);
+            exposed += (uint32_t)__popcll(m);
+            float cx = 0.0f, cy = 0.0f, cz = 0.0f;
+            if (m != 0ull) {  // (the same in every lane)
+                cx = ex_chunk_sum(occ[c] ? 0.0f : sx[c]);
+                cy = ex_chunk_sum(occ[c] ? 0.0f : sy[c]);
+                cz = ex_chunk_sum(occ[c] ? 0.0f : sz[c]);
+            }
+            const bool first = c0 + c == 0u;
+            ex_x = first ? cx : ex_x + cx;
+            ex_y = first ? cy : ex_y + cy;
+            ex_z = first ? cz : ex_z + cz;
+        }
+    }
+    if (lane == 0) {
+        ex.vectors[(size_t)row * 3 + 0] = ex_x;
+        ex.vectors[(size_t)row * 3 + 1] = ex_y;
+        ex.vectors[(size_t)row * 3 + 2] = ex_z;
+        ex.free[row] = exposed;
+        if (a.sasa)  // lib.rs:220-222, as k_accessible_points
+            a.sasa[row] = ((4.0f * 3.14159274101257324219f) * R2) * (float)exposed * (1.0f / (float)a.n_points);
+    }
+}
+
 }  // namespace
 
 // masks[] (and sasa[], if set) of every atom of the binned batch
@@ -602,6 +717,15 @@ void launch_group_points(const GpArgs &g, hipStream_t stream)
     if (!n) return;
     if (g.p.n_points <= 2u * kWave) hipLaunchKernelGGL(k_group_points<2>, dim3(cdiv(n, 4)), dim3(256), 0, stream, g);
     else hipLaunchKernelGGL(k_group_points<4>, dim3(cdiv(n, 4)), dim3(256), 0, stream, g);
+}
+
+// vectors[] and free[] (and p.sasa[], if set) of every atom of the binned batch
+void launch_exposure_vectors(const ExArgs &e, hipStream_t stream)
+{
+    const uint32_t n = e.p.b.n_atoms;
+    if (!n) return;
+    if (e.p.n_points <= 2u * kWave) hipLaunchKernelGGL(k_exposure_vectors<2>, dim3(cdiv(n, 4)), dim3(256), 0, stream, e);
+    else hipLaunchKernelGGL(k_exposure_vectors<4>, dim3(cdiv(n, 4)), dim3(256), 0, stream, e);
 }
 
 }  // namespace rsasa

@@ -290,6 +290,38 @@ class Context:
             ptr(words), ptr(sasa)))
         return words, sasa
 
+    # ---- exposure vectors (in which direction an atom is exposed: the sum of its accessible lattice points) ----
+    def exposure_vectors(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
+        """rsasa_exposure_vectors: (vectors float32[N, 3], free uint32[N], sasa float32[N]).  vectors[i] is the float32 sum
+        of the points of sphere_points(n_points) that are accessible on atom i, in the fixed order the header gives (a
+        tree over each chunk of 64 points, the chunks ascending); free[i] their number, the popcount of
+        accessible_points; sasa equals calculate_sasa_soa.  vectors[i] / free[i] is the mean outward direction;
+        sas_volume() turns vectors and free into the volume the accessible surface encloses."""
+        n_points = _n_points(n_points)
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        vectors = np.zeros((x.shape[0], 3), np.float32)
+        free = np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.rsasa_exposure_vectors(
+            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, ptr(vectors),
+            ptr(free), ptr(sasa)))
+        return vectors, free, sasa
+
+    def exposure_vectors_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
+                               n_points: int = 100):
+        """rsasa_exposure_vectors_batch: exposure_vectors of every structure (one grid each), rows in batch order."""
+        n_points = _n_points(n_points)
+        so = _offsets("structure_offsets", structure_offsets)
+        n_struct = so.shape[0] - 1
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
+        vectors = np.zeros((x.shape[0], 3), np.float32)
+        free = np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.rsasa_exposure_vectors_batch(
+            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
+            ptr(vectors), ptr(free), ptr(sasa)))
+        return vectors, free, sasa
+
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
     def _contact_call(self, call, n_atoms: int):
         """_neighbor_call with the two count columns beside the entries: call(offsets, entries, covered, exclusive,
@@ -534,6 +566,34 @@ def surface_points(words, x, y, z, radius, probe_radius: float = 1.4, n_points: 
     return atom.astype(np.uint32), xyz
 
 
+def sas_volume(vectors, free, x, y, z, radius, probe_radius: float = 1.4, n_points: int = 100, structure_offsets=None,
+               origins=None):
+    """rsasa_sas_volume: (volume float64[S], area float64[S]) of the accessible surface of every structure from the
+    vectors and counts of exposure_vectors[_batch] of these columns: V = sum (a / 3) (R k + (c - o) . E) and
+    A = sum a k with a = 4 pi R^2 / n_points, R = radius + probe_radius (float32), in float64 and atom order on the host
+    (no GPU).  structure_offsets None: one structure.  origins: float64[S, 3] or None for each structure's mean atom
+    centre.  Atoms with a non-finite coordinate or radius are skipped."""
+    n_points = _n_points(n_points)
+    x, y, z, radius, _ = _columns(x, y, z, radius, None)
+    n = x.shape[0]
+    so = np.array([0, n], np.uint32) if structure_offsets is None else _offsets("structure_offsets", structure_offsets)
+    n_struct = so.shape[0] - 1
+    if (int(so[-1]) if n_struct else 0) != n:
+        raise ValueError(f"the offsets cover {int(so[-1]) if n_struct else 0} atoms but the columns hold {n}")
+    vectors = np.ascontiguousarray(vectors, dtype=np.float32)
+    free = np.ascontiguousarray(free, dtype=np.uint32)
+    if vectors.shape != (n, 3) or free.shape != (n,):
+        raise ValueError(f"vectors must have shape [{n}, 3] and free [{n}]")
+    if origins is not None:
+        origins = np.ascontiguousarray(origins, dtype=np.float64)
+        if origins.shape != (n_struct, 3):
+            raise ValueError(f"origins must have shape [{n_struct}, 3]")
+    volume, area = np.zeros(n_struct, np.float64), np.zeros(n_struct, np.float64)
+    check(_capi.load().rsasa_sas_volume(ptr(x), ptr(y), ptr(z), ptr(radius), ptr(vectors), ptr(free), ptr(so), n_struct,
+                                        probe_radius, n_points, ptr(origins), ptr(volume), ptr(area)))
+    return volume, area
+
+
 def contact_areas(counts, offsets, radius, probe_radius: float = 1.4, n_points: int = 100) -> np.ndarray:
     """Counts of contact_points (covered or exclusive) as areas, float32[total] in A^2: the reference's
     ((4 pi R^2) k) / n_points in float32 (src/lib.rs:220-222), k the count and R = radius + probe_radius of the atom
@@ -585,4 +645,4 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 
 
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
-           "contact_areas", "group_areas", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
+           "contact_areas", "group_areas", "sas_volume", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
