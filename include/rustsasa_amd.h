@@ -38,7 +38,8 @@ extern "C" {
  * Additive under 4 (callers detect them by symbol): rsasa_neighbor_t, rsasa_precompute_neighbors,
  * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL; rsasa_accessible_points,
  * rsasa_accessible_points_batch; rsasa_contact_points, rsasa_contact_points_batch; rsasa_group_contacts,
- * rsasa_group_contacts_batch; rsasa_exposure_vectors, rsasa_exposure_vectors_batch, rsasa_sas_volume. */
+ * rsasa_group_contacts_batch; rsasa_exposure_vectors, rsasa_exposure_vectors_batch, rsasa_sas_volume;
+ * rsasa_atom_depth, rsasa_atom_depth_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -502,6 +503,83 @@ int rsasa_sas_volume(const float *x, const float *y, const float *z, const float
                      const uint32_t *structure_offsets, size_t n_structures,
                      float probe_radius, size_t n_points,
                      const double *origins, double *out_volume, double *out_area);
+
+/* ---- atom depth --------------------------------------------------------- */
+
+/* HOW FAR UNDER THE SURFACE an atom lies: per atom the distance from its
+ * centre to the nearest accessible dot of its own structure (atom depth,
+ * Chakravarty & Varadarajan; averaged over a residue: residue depth).  The
+ * other point calls are silent about the atoms with no accessible point; this
+ * one tells them apart.
+ *
+ * Definition.  For a structure with atoms j at centre c_j and radius r_j, probe
+ * p and lattice s = rsasa_sphere_points(n_points), let A_j be the accessible
+ * points of j: exactly the mask of rsasa_accessible_points under the context's
+ * current lane count W.  All arithmetic is float32, unfused, left to right:
+ *
+ *     R_j   = r_j + p
+ *     q     = (c_j.x + R_j * s_k.x, c_j.y + R_j * s_k.y, c_j.z + R_j * s_k.z)
+ *     dx    = c_i.x - q.x            (dy, dz alike)
+ *     d2    = dx * dx + dy * dy + dz * dz
+ *     key_i = min over j in the SAME structure, k in A_j, d2 not NaN,
+ *             of ((uint64_t)bits(d2) << 32) | j
+ *
+ * q is the dot that surface_points() of the Python package lists for (j, k);
+ * d2 >= +0, so its bits order like the numbers; j is the index within the
+ * structure, as in the neighbour entries.  A minimum is exact and has no order,
+ * so the results can be checked bit for bit.
+ *
+ *   out_depth[i]   = sqrtf(d2 of key_i): the correctly rounded float32 square
+ *                    root, taken on the host;
+ *   out_nearest[i] = the low word of key_i: the atom that owns the nearest
+ *                    accessible dot.  Ties in d2 go to the smallest index.  For
+ *                    an exposed atom it is usually i itself;
+ *   an atom for which no accessible dot of its structure has a d2 that is not
+ *   NaN gets out_depth = +inf and out_nearest = 0xFFFFFFFF;
+ *   out_free[i]    (nullable) the exposed count: the popcount of
+ *                    rsasa_accessible_points;
+ *   out_sasa[i]    (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Dots of other structures of a batch never count.  The depth is measured to
+ * the ACCESSIBLE surface (the surface the probe's centre traces); depth - p is
+ * the usual estimate of the distance to the molecular surface, and the library
+ * does not subtract it.
+ *
+ * Non-finite input as rsasa_exposure_vectors: a NaN coordinate or radius is
+ * taken (the atom's own depth is then +inf / 0xFFFFFFFF, its dots have NaN d2
+ * and count for nobody), an infinite coordinate returns
+ * RSASA_ERR_GRID_TOO_LARGE and the context stays usable.  The argument errors
+ * are those of rsasa_exposure_vectors (n_points == 0, probe_radius + largest
+ * radius not a positive finite number, structure_offsets that are not
+ * non-decreasing from 0, NULL columns); out_depth or out_nearest NULL where
+ * there are atoms returns RSASA_ERR_INVALID_ARGUMENT.  No atoms: RSASA_OK.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  The
+ * masks stay on the device; 8 bytes per atom cross the link (and 4 each for
+ * out_free and out_sasa). */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).
+ * out_depth, out_nearest: [n_atoms]; out_free, out_sasa: [n_atoms] or NULL. */
+int rsasa_atom_depth(rsasa_context_t *ctx,
+                     const float *x, const float *y, const float *z, const float *radius,
+                     const uint64_t *id, size_t n_atoms,
+                     float probe_radius, size_t n_points,
+                     float *out_depth, uint32_t *out_nearest,
+                     uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each; an empty
+ * structure is legal).  out_depth, out_nearest:
+ * [structure_offsets[n_structures]]; out_free, out_atom_sasa: the same or NULL.
+ * out_nearest holds indices within the atom's structure. */
+int rsasa_atom_depth_batch(rsasa_context_t *ctx,
+                           const float *x, const float *y, const float *z, const float *radius,
+                           const uint64_t *id,
+                           const uint32_t *structure_offsets, size_t n_structures,
+                           float probe_radius, size_t n_points,
+                           float *out_depth, uint32_t *out_nearest,
+                           uint32_t *out_free, float *out_atom_sasa);
 
 /* ---- contact counts ----------------------------------------------------- */
 

@@ -5,7 +5,7 @@ built from rustsasa_amd/csrc).  Importing this package does not load the
 library; the first call does, and raises if it is missing or no GPU is usable.
 """
 from .engine import (ATOM_DTYPE, NEIGHBOR_DTYPE, Context, RsasaError, contact_areas, device_count, group_areas,
-                     make_atoms, sas_volume, sphere_points, surface_points, unpack_points)
+                     make_atoms, residue_depth, sas_volume, sphere_points, surface_points, unpack_points)
 
 __all__ = ["ATOM_DTYPE", "NEIGHBOR_DTYPE", "Context", "RsasaError", "contact_areas", "device_count", "group_areas",
-           "make_atoms", "sas_volume", "sphere_points", "surface_points", "unpack_points"]
+           "make_atoms", "residue_depth", "sas_volume", "sphere_points", "surface_points", "unpack_points"]

@@ -113,6 +113,10 @@ SYMBOLS = {
                                                C.c_size_t, _vp, _vp, _vp]),
     "rsasa_sas_volume": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                    _vp, _vp, _vp]),
+    "rsasa_atom_depth": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
+                                   _vp, _vp, _vp, _vp]),
+    "rsasa_atom_depth_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,
+                                         C.c_size_t, _vp, _vp, _vp, _vp]),
     "rsasa_contact_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsasa_contact_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,

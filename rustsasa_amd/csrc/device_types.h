@@ -223,6 +223,17 @@ struct ExArgs {
     uint32_t *free;                     // [n_atoms] the exposed points: the popcount of PtArgs::masks
 };
 
+// ---- atom depth (depth.hip, rsasa_atom_depth*) ----
+// A finished point run (p.masks written, in input order) and the grid it ran on: per atom the smallest key over the
+// accessible dots of its structure.
+struct DpArgs {
+    PtArgs p;                           // p.masks, p.words: the masks k_accessible_points wrote; p.sasa as there
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_depth_free)
+    unsigned long long *keys;           // [n_atoms], input order: min of (float bits of d2) << 32 | index within the structure of
+                                        // the dot's owner, over the accessible dots of the atom's structure whose d2 is no NaN
+                                        // (the definition: include/rustsasa_amd.h); all ones where there is none
+};
+
 // ---- contact counts (points.hip, rsasa_contact_points*) ----
 // The same lists and lattice (p.masks unused), per-entry counts out, aligned with NbArgs::out.
 struct CtArgs {
@@ -310,6 +321,8 @@ void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t str
 void launch_accessible_points(const PtArgs &a, hipStream_t stream);
 // The exposed-point sums and counts (points.hip) from those lists.
 void launch_exposure_vectors(const ExArgs &e, hipStream_t stream);
+// The exposed-point counts and the nearest-dot keys (depth.hip) from the masks launch_accessible_points wrote.
+void launch_atom_depth(const DpArgs &d, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);
 // The 64-bit exclusive scan of the count pass by itself (neighbors.hip): a.counts -> a.offsets[0 .. n_atoms], totals -> a.info.

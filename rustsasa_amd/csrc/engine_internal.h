@@ -456,6 +456,8 @@ struct rsasa_context {
     size_t pt_lattice_points = 0;  // the point count pt_lattice holds (0: none)
     // rsasa_exposure_vectors*: the sums and counts of the last call (the lists, lattice and values are the buffers above)
     DeviceBuffer ex_vectors, ex_free;
+    // rsasa_atom_depth*: the nearest-dot keys and the exposed-point counts of the last call (the masks are pt_masks)
+    DeviceBuffer dp_keys, dp_free;
     // rsasa_contact_points*: the per-entry counts of the last call (the lists, lattice and values are the buffers above)
     DeviceBuffer ct_covered, ct_exclusive;
     // rsasa_group_contacts*: the labels, the lists in label order with their own-group and row counts, the row offsets,

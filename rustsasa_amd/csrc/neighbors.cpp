@@ -2,11 +2,13 @@
 // batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws), then
 // neighbors.hip counts, scans and fills the lists.  The accessible-point entry points (rsasa_accessible_points /
 // _batch) run the same stages and hand the lists, still on the device, to points.hip; so do the exposure vectors
-// (rsasa_exposure_vectors*), the contact counts (rsasa_contact_points*) and the group contacts (rsasa_group_contacts*).
+// (rsasa_exposure_vectors*), the contact counts (rsasa_contact_points*) and the group contacts (rsasa_group_contacts*);
+// the atom depths (rsasa_atom_depth*) run the point masks and hand them and the grid to depth.hip.
 // rsasa_sas_volume is plain host arithmetic on what the exposure vectors return.  Host code only.
 #include "engine_internal.h"
 
 #include <cmath>
+#include <cstring>
 
 namespace {
 
@@ -237,6 +239,62 @@ int ex_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     RS_HIP(ctx, hipMemcpyAsync(out_free, e.free, N * 4, hipMemcpyDeviceToHost, st));
     if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, e.p.sasa, N * 4, hipMemcpyDeviceToHost, st));
     RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+// ---- atom depth (rsasa_atom_depth*) ----
+
+// One run of the atom depths: pt_run's stages up to the masks, which stay on the device (pt_masks); k_depth_free counts
+// them and k_atom_depth searches the grid for every atom's nearest accessible dot.  8 bytes per atom come back (and 4
+// each for the counts and the values, if asked); the square root of the key's d2 is taken here (sqrtf: correctly rounded).
+int dp_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *so, size_t S, size_t N, float probe, size_t n_points, float *out_depth, uint32_t *out_nearest,
+           uint32_t *out_free, float *out_sasa)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) return RSASA_OK;
+    const size_t words = (n_points + 31) / 32;
+    size_t padded = 0;
+    if ((rc = pt_lattice(ctx, n_points, padded))) return rc;
+    NbArgs a{};
+    NbInfo info{};
+    if ((rc = nb_count(ctx, x, y, z, r, id, so, S, N, nullptr, probe, __builtin_nanf(""), nullptr, a, info))) return rc;
+    if (info.total && (rc = nb_fill(ctx, a, info))) return rc;
+    if ((rc = reserve(ctx, ctx->pt_masks, N * words * 4)) || (rc = reserve(ctx, ctx->dp_keys, N * 8)) ||
+        (rc = reserve(ctx, ctx->dp_free, N * 4)) || (out_sasa && (rc = reserve(ctx, ctx->pt_sasa, N * 4))))
+        return rc;
+    DpArgs d{};
+    d.p.b = a.b;
+    d.p.offsets = a.offsets;
+    d.p.entries = (const uint2 *)ctx->nb_entries.p;  // (not read when every list is empty)
+    const float *lat = (const float *)ctx->pt_lattice.p;
+    d.p.lx = lat; d.p.ly = lat + padded; d.p.lz = lat + 2 * padded;
+    d.p.n_points = (uint32_t)n_points;
+    d.p.n_fused = (uint32_t)(n_points - n_points % (size_t)ctx->simd_width);
+    d.p.words = (uint32_t)words;
+    d.p.masks = (uint32_t *)ctx->pt_masks.p;
+    d.p.sasa = out_sasa ? (float *)ctx->pt_sasa.p : nullptr;
+    d.free = (uint32_t *)ctx->dp_free.p;
+    d.keys = (unsigned long long *)ctx->dp_keys.p;
+    hipStream_t st = ctx->stream;
+    launch_accessible_points(d.p, st);
+    launch_atom_depth(d, st);
+    RS_HIP(ctx, hipGetLastError());
+    std::vector<uint64_t> keys(N);
+    RS_HIP(ctx, hipMemcpyAsync(keys.data(), d.keys, N * 8, hipMemcpyDeviceToHost, st));
+    if (out_free) RS_HIP(ctx, hipMemcpyAsync(out_free, d.free, N * 4, hipMemcpyDeviceToHost, st));
+    if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, d.p.sasa, N * 4, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    for (size_t i = 0; i < N; i++) {
+        const uint64_t k = keys[i];
+        const uint32_t hi = (uint32_t)(k >> 32);
+        float d2;
+        std::memcpy(&d2, &hi, 4);
+        out_depth[i] = k == ~0ull ? __builtin_inff() : sqrtf(d2);
+        out_nearest[i] = (uint32_t)k;
+    }
     return RSASA_OK;
 }
 
@@ -510,6 +568,39 @@ int rsasa_exposure_vectors_batch(rsasa_context_t *ctx, const float *x, const flo
     if (N && (!x || !y || !z || !radius || !out_vectors || !out_free)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
     return ex_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_vectors, out_free,
                   out_atom_sasa);
+}
+
+int rsasa_atom_depth(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                     const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, float *out_depth,
+                     uint32_t *out_nearest, uint32_t *out_free, float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (n_atoms && (!x || !y || !z || !radius || !out_depth || !out_nearest)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
+    if (n_atoms >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    const uint32_t so[2] = {0u, (uint32_t)n_atoms};
+    return dp_run(ctx, x, y, z, radius, id, so, 1, n_atoms, probe_radius, n_points, out_depth, out_nearest, out_free, out_sasa);
+}
+
+int rsasa_atom_depth_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                           const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                           size_t n_points, float *out_depth, uint32_t *out_nearest, uint32_t *out_free, float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!structure_offsets) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
+    if (n_structures >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "too many structures");
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1])
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (n_structures && structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets[0] must be 0");
+    if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    if (N && (!x || !y || !z || !radius || !out_depth || !out_nearest)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    return dp_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_depth, out_nearest,
+                  out_free, out_atom_sasa);
 }
 
 // No context, no device: double arithmetic in atom order on the host.

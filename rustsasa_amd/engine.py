@@ -322,6 +322,41 @@ class Context:
             ptr(vectors), ptr(free), ptr(sasa)))
         return vectors, free, sasa
 
+    # ---- atom depth (how far under the accessible surface an atom lies: its nearest accessible dot) ----
+    def atom_depth(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
+        """rsasa_atom_depth: (depth float32[N], nearest uint32[N], free uint32[N], sasa float32[N]).  depth[i] is the
+        float32 distance from atom i's centre to the nearest dot of surface_points() of the structure's accessible
+        points, evaluated as the header defines it (plain float32, so it can be checked bit for bit); nearest[i] the atom
+        that owns that dot (ties: the smallest index); +inf and 0xFFFFFFFF where there is no such dot.  free[i] is the
+        popcount of accessible_points, sasa equals calculate_sasa_soa.  depth - probe_radius estimates the distance to
+        the molecular surface; residue_depth() averages depth over residues."""
+        n_points = _n_points(n_points)
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        depth = np.zeros(x.shape[0], np.float32)
+        nearest = np.zeros(x.shape[0], np.uint32)
+        free = np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.rsasa_atom_depth(
+            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, ptr(depth),
+            ptr(nearest), ptr(free), ptr(sasa)))
+        return depth, nearest, free, sasa
+
+    def atom_depth_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100):
+        """rsasa_atom_depth_batch: atom_depth of every structure (one grid each, dots of other structures never count),
+        rows in batch order; nearest holds indices within the atom's structure."""
+        n_points = _n_points(n_points)
+        so = _offsets("structure_offsets", structure_offsets)
+        n_struct = so.shape[0] - 1
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
+        depth = np.zeros(x.shape[0], np.float32)
+        nearest = np.zeros(x.shape[0], np.uint32)
+        free = np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(self._lib.rsasa_atom_depth_batch(
+            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
+            ptr(depth), ptr(nearest), ptr(free), ptr(sasa)))
+        return depth, nearest, free, sasa
+
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
     def _contact_call(self, call, n_atoms: int):
         """_neighbor_call with the two count columns beside the entries: call(offsets, entries, covered, exclusive,
@@ -566,6 +601,30 @@ def surface_points(words, x, y, z, radius, probe_radius: float = 1.4, n_points: 
     return atom.astype(np.uint32), xyz
 
 
+def residue_depth(depth, residue_offsets):
+    """Residue depth: the float64 mean of the atom depths (atom_depth[_batch]) of every residue, residue r being atoms
+    [residue_offsets[r], residue_offsets[r + 1]); NaN for an empty residue.  Host arithmetic: each residue's depths are
+    added in float64 in atom order and divided by their number (an atom at +inf makes its residue +inf)."""
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    ro = np.asarray(residue_offsets)
+    if ro.dtype.kind not in "ui":
+        raise ValueError(f"residue_offsets must be an array of integers, not {ro.dtype}")
+    ro = ro.astype(np.int64)
+    if depth.ndim != 1 or ro.ndim != 1 or ro.shape[0] < 1:
+        raise ValueError("depth and residue_offsets must be 1-D arrays, residue_offsets of at least one entry")
+    if ro[0] < 0 or (np.diff(ro) < 0).any() or ro[-1] > depth.shape[0]:
+        raise ValueError("residue_offsets must be non-decreasing and stay within depth")
+    out = np.full(ro.shape[0] - 1, np.nan, np.float64)
+    for r in range(ro.shape[0] - 1):
+        b, e = int(ro[r]), int(ro[r + 1])
+        if e > b:
+            total = 0.0
+            for v in depth[b:e].astype(np.float64):
+                total += float(v)
+            out[r] = total / (e - b)
+    return out
+
+
 def sas_volume(vectors, free, x, y, z, radius, probe_radius: float = 1.4, n_points: int = 100, structure_offsets=None,
                origins=None):
     """rsasa_sas_volume: (volume float64[S], area float64[S]) of the accessible surface of every structure from the
@@ -645,4 +704,4 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 
 
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
-           "contact_areas", "group_areas", "sas_volume", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
+           "contact_areas", "group_areas", "sas_volume", "residue_depth", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
