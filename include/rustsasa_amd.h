@@ -581,6 +581,95 @@ int rsasa_atom_depth_batch(rsasa_context_t *ctx,
                            float *out_depth, uint32_t *out_nearest,
                            uint32_t *out_free, float *out_atom_sasa);
 
+/* ---- surface components ------------------------------------------------- */
+
+/* WHICH SURFACE a free point belongs to: every accessible dot of a structure
+ * labelled by the connected piece of accessible surface it lies on.  A dot on
+ * the wall of an internal cavity counts in the SASA value, in rsasa_sas_volume
+ * and in rsasa_atom_depth exactly like one that faces bulk solvent; the labels
+ * tell them apart.  The result is per dot and not per atom: one atom can own
+ * dots on two surfaces.
+ *
+ * Definition.  Take one structure, probe p, lattice
+ * s = rsasa_sphere_points(n_points); A_j is the mask of rsasa_accessible_points
+ * under the context's current lane count W.
+ *
+ *   Dots.   The dots of the structure are the pairs (j, k) with k in A_j,
+ *           ordered by (j, k) ascending; a dot's number is its position in
+ *           that order, starting at 0 for each structure.
+ *   Place.  Float32, unfused, as in rsasa_atom_depth:
+ *               R_j = r_j + p
+ *               q   = (c_j.x + R_j * s_k.x, c_j.y + R_j * s_k.y, c_j.z + R_j * s_k.z)
+ *   Edges.  Two different dots a, b of the same structure are linked when
+ *               dx = q_a.x - q_b.x            (dy, dz alike)
+ *               d2 = dx * dx + dy * dy + dz * dz
+ *               d2 <= link * link             (one float32 product)
+ *           A NaN d2 links nothing.  The test is symmetric, because negation
+ *           is exact.  Atom ids play no part.
+ *   Label.  A component is a connected component of that graph; a dot's label
+ *           is the smallest dot number in its component.  A dot whose label
+ *           equals its own number is its component's representative.
+ *
+ * A minimum over a set has no order, so the labels can be checked bit for bit
+ * with no tolerance anywhere, whatever the schedule of the GPU.
+ *
+ *   out_dot_offsets  [n + 1], the exclusive scan of the free counts: atom i's
+ *                    dots are [out_dot_offsets[i], out_dot_offsets[i + 1]).  In
+ *                    the batch form it is batch-global, like out_offsets of the
+ *                    neighbour calls.
+ *   out_labels       out_labels[out_dot_offsets[i] .. out_dot_offsets[i + 1])
+ *                    are the labels of atom i's accessible points, in ascending
+ *                    point order.  Labels are relative to the structure:
+ *                    subtract out_dot_offsets[structure_offsets[s]] from an
+ *                    array position to get a dot number of structure s.
+ *   out_free[i]      (nullable) the exposed count: the popcount of
+ *                    rsasa_accessible_points;
+ *   out_sasa[i]      (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Sizing, as the neighbour calls: out_dot_offsets is always written (on
+ * success and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_labels is NULL or
+ * labels_capacity < out_dot_offsets[n], nothing else is written and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned: call once to size, allocate, call
+ * again.
+ *
+ * link must be finite and >= 0 (link = 0 links coinciding dots only); NaN, a
+ * negative or an infinite link returns RSASA_ERR_INVALID_ARGUMENT, and so does
+ * a batch with 2^32 or more dots.  The remaining argument errors and the
+ * non-finite input rules are those of rsasa_atom_depth: a NaN coordinate or
+ * radius is taken (the atom's mask is all ones, its dots have NaN positions, so
+ * each is a component of its own), an infinite coordinate returns
+ * RSASA_ERR_GRID_TOO_LARGE and the context stays usable.  No atoms: RSASA_OK
+ * with out_dot_offsets[0] = 0.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  The
+ * masks and lists stay on the device; 8 bytes per atom and 4 per dot cross the
+ * link (and 4 per atom each for out_free and out_sasa). */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).
+ * out_dot_offsets: [n_atoms + 1]; out_labels: [labels_capacity]; out_free,
+ * out_sasa: [n_atoms] or NULL. */
+int rsasa_surface_components(rsasa_context_t *ctx,
+                             const float *x, const float *y, const float *z, const float *radius,
+                             const uint64_t *id, size_t n_atoms,
+                             float probe_radius, size_t n_points, float link,
+                             uint64_t *out_dot_offsets,
+                             uint32_t *out_labels, size_t labels_capacity,
+                             uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each; an empty
+ * structure is legal); dots of different structures are never linked.
+ * out_dot_offsets is batch-global [structure_offsets[n_structures] + 1]. */
+int rsasa_surface_components_batch(rsasa_context_t *ctx,
+                                   const float *x, const float *y, const float *z, const float *radius,
+                                   const uint64_t *id,
+                                   const uint32_t *structure_offsets, size_t n_structures,
+                                   float probe_radius, size_t n_points, float link,
+                                   uint64_t *out_dot_offsets,
+                                   uint32_t *out_labels, size_t labels_capacity,
+                                   uint32_t *out_free, float *out_atom_sasa);
+
 /* ---- contact counts ----------------------------------------------------- */
 
 /* WHICH neighbour buries which part of an atom: per entry of each atom's

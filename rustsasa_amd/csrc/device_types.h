@@ -234,6 +234,19 @@ struct DpArgs {
                                         // (the definition: include/rustsasa_amd.h); all ones where there is none
 };
 
+// ---- surface components (components.hip, rsasa_surface_components*) ----
+// A finished point run (p.masks written, in input order) and the grid it ran on: the accessible dots numbered through the
+// batch in (atom, point) order and, per dot, the smallest dot of its connected component.
+struct CcArgs {
+    PtArgs p;                           // p.masks, p.words: the masks k_accessible_points wrote; p.sasa as there
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_component_free)
+    const unsigned long long *dot_offsets;  // [n_atoms + 1] exclusive scan of free: atom i's dots are [dot_offsets[i], dot_offsets[i + 1])
+    unsigned long long n_dots;          // dot_offsets[n_atoms], below 2^32
+    uint32_t *parent;                   // [n_dots] the union-find forest: parent <= self, a root is the smallest dot of its tree
+    uint32_t *labels;                   // [n_dots] the root of the dot's tree minus the first dot of its structure
+    float link, link2;                  // two dots are linked when d2 <= link2 = link * link (one float32 product)
+};
+
 // ---- contact counts (points.hip, rsasa_contact_points*) ----
 // The same lists and lattice (p.masks unused), per-entry counts out, aligned with NbArgs::out.
 struct CtArgs {
@@ -323,6 +336,10 @@ void launch_accessible_points(const PtArgs &a, hipStream_t stream);
 void launch_exposure_vectors(const ExArgs &e, hipStream_t stream);
 // The exposed-point counts and the nearest-dot keys (depth.hip) from the masks launch_accessible_points wrote.
 void launch_atom_depth(const DpArgs &d, hipStream_t stream);
+// The exposed-point counts (components.hip) from the masks launch_accessible_points wrote; then, with CcArgs::dot_offsets,
+// the component labels of the dots.
+void launch_component_free(const CcArgs &c, hipStream_t stream);
+void launch_components(const CcArgs &c, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);
 // The 64-bit exclusive scan of the count pass by itself (neighbors.hip): a.counts -> a.offsets[0 .. n_atoms], totals -> a.info.

@@ -458,6 +458,9 @@ struct rsasa_context {
     DeviceBuffer ex_vectors, ex_free;
     // rsasa_atom_depth*: the nearest-dot keys and the exposed-point counts of the last call (the masks are pt_masks)
     DeviceBuffer dp_keys, dp_free;
+    // rsasa_surface_components*: the dot offsets, the union-find forest and the labels of the last call (the masks are
+    // pt_masks, the exposed-point counts dp_free)
+    DeviceBuffer cc_offsets, cc_parent, cc_labels;
     // rsasa_contact_points*: the per-entry counts of the last call (the lists, lattice and values are the buffers above)
     DeviceBuffer ct_covered, ct_exclusive;
     // rsasa_group_contacts*: the labels, the lists in label order with their own-group and row counts, the row offsets,

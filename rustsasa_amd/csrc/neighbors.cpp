@@ -3,7 +3,8 @@
 // neighbors.hip counts, scans and fills the lists.  The accessible-point entry points (rsasa_accessible_points /
 // _batch) run the same stages and hand the lists, still on the device, to points.hip; so do the exposure vectors
 // (rsasa_exposure_vectors*), the contact counts (rsasa_contact_points*) and the group contacts (rsasa_group_contacts*);
-// the atom depths (rsasa_atom_depth*) run the point masks and hand them and the grid to depth.hip.
+// the atom depths (rsasa_atom_depth*) run the point masks and hand them and the grid to depth.hip, the surface
+// components (rsasa_surface_components*) hand the same to components.hip.
 // rsasa_sas_volume is plain host arithmetic on what the exposure vectors return.  Host code only.
 #include "engine_internal.h"
 
@@ -298,6 +299,77 @@ int dp_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     return RSASA_OK;
 }
 
+// ---- surface components (rsasa_surface_components*) ----
+
+// One run of the surface components: dp_run's stages up to the masks, which stay on the device (pt_masks);
+// k_component_free counts them, the scan of the neighbour counts turns the counts into out_offsets, the caller's label
+// buffer is checked against out_offsets[N] as nb_run checks its entries, and the union-find kernels label the dots.
+// 8 bytes per atom and 4 per dot come back (and 4 per atom each for the counts and the values, if asked).
+int cc_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id,
+           const uint32_t *so, size_t S, size_t N, float probe, size_t n_points, float link, uint64_t *out_offsets,
+           uint32_t *out_labels, size_t cap, uint32_t *out_free, float *out_sasa)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    int rc;
+    if (N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    const size_t words = (n_points + 31) / 32;
+    size_t padded = 0;
+    if ((rc = pt_lattice(ctx, n_points, padded))) return rc;
+    NbArgs a{};
+    NbInfo info{};
+    if ((rc = nb_count(ctx, x, y, z, r, id, so, S, N, nullptr, probe, __builtin_nanf(""), nullptr, a, info))) return rc;
+    if (info.total && (rc = nb_fill(ctx, a, info))) return rc;
+    if ((rc = reserve(ctx, ctx->pt_masks, N * words * 4)) || (rc = reserve(ctx, ctx->dp_free, N * 4)) ||
+        (rc = reserve(ctx, ctx->cc_offsets, (N + 1) * 8)) || (out_sasa && (rc = reserve(ctx, ctx->pt_sasa, N * 4))))
+        return rc;
+    CcArgs c{};
+    c.p.b = a.b;
+    c.p.offsets = a.offsets;
+    c.p.entries = (const uint2 *)ctx->nb_entries.p;  // (not read when every list is empty)
+    const float *lat = (const float *)ctx->pt_lattice.p;
+    c.p.lx = lat; c.p.ly = lat + padded; c.p.lz = lat + 2 * padded;
+    c.p.n_points = (uint32_t)n_points;
+    c.p.n_fused = (uint32_t)(n_points - n_points % (size_t)ctx->simd_width);
+    c.p.words = (uint32_t)words;
+    c.p.masks = (uint32_t *)ctx->pt_masks.p;
+    c.p.sasa = out_sasa ? (float *)ctx->pt_sasa.p : nullptr;
+    c.free = (uint32_t *)ctx->dp_free.p;
+    c.dot_offsets = (const unsigned long long *)ctx->cc_offsets.p;
+    c.link = link;
+    c.link2 = link * link;
+    hipStream_t st = ctx->stream;
+    launch_accessible_points(c.p, st);
+    launch_component_free(c, st);
+    NbArgs scan = a;  // (the neighbour run has read its parts and its info)
+    scan.counts = c.free;
+    scan.offsets = (unsigned long long *)ctx->cc_offsets.p;
+    launch_neighbor_scan(scan, st);
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, hipMemcpyAsync(out_offsets, c.dot_offsets, (N + 1) * 8, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    const uint64_t n_dots = out_offsets[N];
+    if (n_dots >= 0x100000000ull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "2^32 or more accessible dots");
+    if (!out_labels || cap < n_dots)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_labels is NULL or holds fewer labels than out_dot_offsets[n]");
+    if (n_dots) {
+        if ((rc = reserve(ctx, ctx->cc_parent, n_dots * 4)) || (rc = reserve(ctx, ctx->cc_labels, n_dots * 4))) return rc;
+        c.n_dots = n_dots;
+        c.parent = (uint32_t *)ctx->cc_parent.p;
+        c.labels = (uint32_t *)ctx->cc_labels.p;
+        launch_components(c, st);
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, hipMemcpyAsync(out_labels, c.labels, n_dots * 4, hipMemcpyDeviceToHost, st));
+    }
+    if (out_free) RS_HIP(ctx, hipMemcpyAsync(out_free, c.free, N * 4, hipMemcpyDeviceToHost, st));
+    if (out_sasa) RS_HIP(ctx, hipMemcpyAsync(out_sasa, c.p.sasa, N * 4, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
 // ---- contact counts (rsasa_contact_points*) ----
 
 // One run of the contact counts: the lists of pt_run, sized and copied out as by nb_run, and k_contact_points' counts
@@ -354,6 +426,16 @@ int ct_check(rsasa_context *ctx, size_t N, const float *x, const float *y, const
     if (!out_offsets || (N && (!x || !y || !z || !radius))) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_points == 0 || n_points >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^31 - 1)");
     if (N >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "more than 2^31 - 1 atoms");
+    return RSASA_OK;
+}
+
+// ct_check, and the link length: finite and not negative.
+int cc_check(rsasa_context *ctx, size_t N, const float *x, const float *y, const float *z, const float *radius,
+             size_t n_points, float link, const uint64_t *out_offsets)
+{
+    int rc;
+    if ((rc = ct_check(ctx, N, x, y, z, radius, n_points, out_offsets))) return rc;
+    if (!(link >= 0.0f) || std::isinf(link)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "link must be finite and not negative");
     return RSASA_OK;
 }
 
@@ -601,6 +683,38 @@ int rsasa_atom_depth_batch(rsasa_context_t *ctx, const float *x, const float *y,
     if (N && (!x || !y || !z || !radius || !out_depth || !out_nearest)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
     return dp_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, out_depth, out_nearest,
                   out_free, out_atom_sasa);
+}
+
+int rsasa_surface_components(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                             const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, float link,
+                             uint64_t *out_dot_offsets, uint32_t *out_labels, size_t labels_capacity, uint32_t *out_free,
+                             float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if ((rc = cc_check(ctx, n_atoms, x, y, z, radius, n_points, link, out_dot_offsets))) return rc;
+    const uint32_t so[2] = {0u, (uint32_t)n_atoms};
+    return cc_run(ctx, x, y, z, radius, id, so, 1, n_atoms, probe_radius, n_points, link, out_dot_offsets, out_labels,
+                  labels_capacity, out_free, out_sasa);
+}
+
+int rsasa_surface_components_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                                   const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures,
+                                   float probe_radius, size_t n_points, float link, uint64_t *out_dot_offsets,
+                                   uint32_t *out_labels, size_t labels_capacity, uint32_t *out_free, float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!structure_offsets) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_structures >= 0x7FFFFFFFull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "too many structures");
+    for (size_t s = 0; s < n_structures; s++)
+        if (structure_offsets[s] > structure_offsets[s + 1])
+            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
+    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    if (n_structures && structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets[0] must be 0");
+    if ((rc = cc_check(ctx, N, x, y, z, radius, n_points, link, out_dot_offsets))) return rc;
+    return cc_run(ctx, x, y, z, radius, id, structure_offsets, n_structures, N, probe_radius, n_points, link, out_dot_offsets,
+                  out_labels, labels_capacity, out_free, out_atom_sasa);
 }
 
 // No context, no device: double arithmetic in atom order on the host.

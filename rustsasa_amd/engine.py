@@ -357,6 +357,58 @@ class Context:
             ptr(depth), ptr(nearest), ptr(free), ptr(sasa)))
         return depth, nearest, free, sasa
 
+    # ---- surface components (which connected piece of accessible surface a free point lies on) ----
+    def _component_call(self, call, n_atoms: int, n_points: int):
+        """The size-then-fill pattern of _contact_call for labels: call(dot_offsets, labels, capacity) with a guessed
+        capacity, and once more at dot_offsets[-1] labels when that was too small; returns (dot_offsets uint64[N + 1],
+        labels uint32[dots])."""
+        offsets = np.zeros(n_atoms + 1, np.uint64)
+        labels = np.empty(min(n_points, 32) * n_atoms, np.uint32)
+        rc = call(offsets, labels, labels.shape[0])
+        if rc == _capi.RSASA_ERR_BUFFER_TOO_SMALL:
+            labels = np.empty(int(offsets[-1]), np.uint32)
+            rc = call(offsets, labels, labels.shape[0])
+        self._check(rc)
+        return offsets, labels[:int(offsets[-1])]
+
+    def surface_components(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, link=None):
+        """rsasa_surface_components: (dot_offsets uint64[N + 1], labels uint32[dots], free uint32[N], sasa float32[N]).
+        The accessible dots (surface_points' rows: atoms in order, each atom's points in lattice order) are numbered
+        from 0; two dots no further apart than `link` (float32 d2 <= link * link) are linked, and labels[d] is the
+        smallest dot number of d's connected component.  Atom i's dots are [dot_offsets[i], dot_offsets[i + 1]).
+        link None: default_link(radius, probe_radius, n_points).  free is the popcount of accessible_points, sasa
+        equals calculate_sasa_soa.  component_table() ranks the components, split_sasa() splits each atom's area into
+        the largest component's and the rest."""
+        n_points = _n_points(n_points)
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        link = default_link(radius, probe_radius, n_points) if link is None else link
+        free, sasa = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, labels, cap):
+            return self._lib.rsasa_surface_components(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, link,
+                ptr(offsets), ptr(labels), cap, ptr(free), ptr(sasa))
+        return self._component_call(call, x.shape[0], n_points) + (free, sasa)
+
+    def surface_components_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
+                                 n_points: int = 100, link=None):
+        """rsasa_surface_components_batch: surface_components of every structure (one grid each, dots of different
+        structures are never linked).  dot_offsets runs over the whole batch; labels are dot numbers within the
+        structure (subtract dot_offsets[structure_offsets[s]] from a position to get one).  link None: default_link of
+        the whole batch's radii."""
+        n_points = _n_points(n_points)
+        so = _offsets("structure_offsets", structure_offsets)
+        n_struct = so.shape[0] - 1
+        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
+        link = default_link(radius, probe_radius, n_points) if link is None else link
+        free, sasa = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, labels, cap):
+            return self._lib.rsasa_surface_components_batch(
+                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points, link,
+                ptr(offsets), ptr(labels), cap, ptr(free), ptr(sasa))
+        return self._component_call(call, x.shape[0], n_points) + (free, sasa)
+
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
     def _contact_call(self, call, n_atoms: int):
         """_neighbor_call with the two count columns beside the entries: call(offsets, entries, covered, exclusive,
@@ -625,6 +677,92 @@ def residue_depth(depth, residue_offsets):
     return out
 
 
+def default_link(radius, probe_radius: float = 1.4, n_points: int = 100) -> np.float32:
+    """The link length surface_components uses when none is given: float32(1.5 * sqrt(4 pi / n_points) * (max_r + probe)),
+    max_r the largest finite radius folded from 0, computed in float64 and rounded once.  sqrt(4 pi / n_points) * R is
+    the side of the square that one dot's share of a sphere of radius R would fill; one and a half of that spans the
+    largest gap between neighbouring dots of one sphere (1.42 A of 1.7441 A for ProtOr radii, probe 1.4 and 100 points)."""
+    n_points = _n_points(n_points)
+    r = np.asarray(radius, dtype=np.float32).astype(np.float64)
+    r = r[np.isfinite(r)]
+    max_r = max(0.0, float(r.max())) if r.size else 0.0
+    return np.float32(1.5 * np.sqrt(4.0 * np.pi / n_points) * (max_r + float(probe_radius)))
+
+
+def _dots(dot_offsets, labels, radius, probe_radius, n_points, structure_offsets):
+    """The checked arguments of component_table / split_sasa: (dot offsets int64[N + 1], labels int64[D], structure
+    offsets int64[S + 1], owner int64[D], dot area float64[D])."""
+    n_points = _n_points(n_points)
+    radius = _f32(radius)
+    n = radius.shape[0]
+    off = np.ascontiguousarray(dot_offsets, dtype=np.uint64).astype(np.int64)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32).astype(np.int64)
+    if radius.ndim != 1 or off.ndim != 1 or off.shape[0] != n + 1:
+        raise ValueError(f"dot_offsets must be a 1-D array of {n + 1} entries (one per atom, and the end)")
+    sizes = np.diff(off)
+    if off[0] != 0 or (sizes < 0).any():
+        raise ValueError("dot_offsets must be non-decreasing from 0")
+    if labels.ndim != 1 or labels.shape[0] != int(off[-1]):
+        raise ValueError(f"labels must be a 1-D array of dot_offsets[-1] = {int(off[-1])} entries")
+    so = np.array([0, n], np.int64) if structure_offsets is None else \
+        _offsets("structure_offsets", structure_offsets).astype(np.int64)
+    if (int(so[-1]) if so.shape[0] > 1 else 0) != n or so[0] != 0 or (np.diff(so) < 0).any():
+        raise ValueError(f"structure_offsets must be non-decreasing from 0 to the {n} atoms of radius")
+    owner = np.repeat(np.arange(n, dtype=np.int64), sizes)
+    with np.errstate(invalid="ignore", over="ignore"):
+        R = (radius + np.float32(probe_radius)).astype(np.float64)
+        area = (4.0 * np.pi * (R * R) / n_points)[owner]
+    return off, labels, so, owner, area
+
+
+def component_table(dot_offsets, labels, radius, probe_radius: float = 1.4, n_points: int = 100, structure_offsets=None):
+    """The components of surface_components[_batch] per structure, ranked: (component_offsets int64[S + 1],
+    label uint32[C], dots int64[C], area float64[C], atoms int64[C]).  Structure s owns rows
+    [component_offsets[s], component_offsets[s + 1]), sorted by area descending, ties to the smaller label; label is
+    the component's representative dot (a dot number within the structure), dots its size, area the float64 sum of
+    4 pi R^2 / n_points over its dots in dot order (R = radius + probe_radius in float32, of the dot's atom), atoms how
+    many atoms own a dot of it.  structure_offsets None: one structure.  Host arithmetic (a bincount of the labels)."""
+    off, labels, so, owner, area = _dots(dot_offsets, labels, radius, probe_radius, n_points, structure_offsets)
+    n_struct = so.shape[0] - 1
+    c_off = np.zeros(n_struct + 1, np.int64)
+    cols = ([], [], [], [])
+    for s in range(n_struct):
+        b, e = int(off[so[s]]), int(off[so[s + 1]])
+        lab = labels[b:e]
+        if lab.size and int(lab.max()) >= e - b:
+            raise ValueError(f"a label of structure {s} is no dot number of it")
+        uniq = np.unique(lab)
+        n_dots = np.bincount(lab, minlength=e - b)[uniq]
+        a = np.bincount(lab, weights=area[b:e], minlength=e - b)[uniq]
+        pairs = np.unique((lab << 32) | (owner[b:e] - so[s]))
+        n_atoms = np.bincount(pairs >> 32, minlength=e - b)[uniq]
+        order = np.lexsort((uniq, -a))
+        for col, v in zip(cols, (uniq, n_dots, a, n_atoms)):
+            col.append(v[order])
+        c_off[s + 1] = c_off[s] + uniq.shape[0]
+    cat = [np.concatenate(c) if c else np.zeros(0) for c in cols]
+    return c_off, cat[0].astype(np.uint32), cat[1].astype(np.int64), cat[2].astype(np.float64), cat[3].astype(np.int64)
+
+
+def split_sasa(dot_offsets, labels, radius, probe_radius: float = 1.4, n_points: int = 100, structure_offsets=None):
+    """(outer float64[N], cavity float64[N]): every atom's accessible area split into the part that lies on its
+    structure's first-ranked component of component_table (the largest by area) and the rest, each the float64 sum of
+    4 pi R^2 / n_points over the atom's dots there.  Calling the largest component the outer surface is a convention
+    for single-body structures (a protein with internal voids); a structure of several bodies has several outer
+    surfaces, and its callers choose from component_table."""
+    off, labels, so, owner, area = _dots(dot_offsets, labels, radius, probe_radius, n_points, structure_offsets)
+    c_off, label = component_table(dot_offsets, labels, radius, probe_radius, n_points, structure_offsets)[:2]
+    n = off.shape[0] - 1
+    is_outer = np.zeros(labels.shape[0], bool)
+    for s in range(so.shape[0] - 1):
+        b, e = int(off[so[s]]), int(off[so[s + 1]])
+        if e > b:
+            is_outer[b:e] = labels[b:e] == int(label[c_off[s]])
+    outer = np.bincount(owner[is_outer], weights=area[is_outer], minlength=n)
+    cavity = np.bincount(owner[~is_outer], weights=area[~is_outer], minlength=n)
+    return outer, cavity
+
+
 def sas_volume(vectors, free, x, y, z, radius, probe_radius: float = 1.4, n_points: int = 100, structure_offsets=None,
                origins=None):
     """rsasa_sas_volume: (volume float64[S], area float64[S]) of the accessible surface of every structure from the
@@ -704,4 +842,5 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 
 
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
-           "contact_areas", "group_areas", "sas_volume", "residue_depth", "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
+           "contact_areas", "group_areas", "sas_volume", "residue_depth", "default_link", "component_table", "split_sasa",
+           "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
