@@ -6,8 +6,10 @@ followed literally.
     edge    dx = q_a.x - q_b.x, ...; d2 = dx*dx + dy*dy + dz*dz; d2 <= link * link (numpy float32: nothing is fused)
     label   the smallest dot number of the dot's connected component
 
-Candidate pairs come from a float64 k-d tree at link * (1 + 1e-5) + 1e-4, a superset of the real edges for coordinates
-below 10^4 (float32 rounding of q and d2 is far below 1e-4 there); each candidate is decided by the float32 expression.
+Candidate pairs come from a float64 k-d tree over the float32 dots at link * (1 + 1e-5) + 1e-4, a superset of the real
+edges (the float32 d2 of two dots differs from their exact squared distance by a few 2^-24 of itself, whatever the size
+of the coordinates; they are kept below 10^6, raised from 10^4 for the cases of sweep_cases.py that sit at the
+margins' limit near 2.15e5 A); each candidate is decided by the float32 expression.
 Dots with a non-finite position have a NaN d2 against everybody and are left out of the tree.  The masks come from
 points_model.py (pinned to the oracle).  A minimum over a set has no order: no tolerance anywhere.  Plain helper module
 (not a conftest)."""
@@ -28,7 +30,9 @@ def edges_of(qx, qy, qz, link):
     ok = np.flatnonzero(np.isfinite(qx) & np.isfinite(qy) & np.isfinite(qz))
     if len(ok) < 2:
         return np.zeros((0, 2), np.int64)
-    assert max(np.abs(qx[ok]).max(), np.abs(qy[ok]).max(), np.abs(qz[ok]).max()) < 1e4
+    # (the tree sees the float32 dots exactly, and the float32 d2 of two of them is within a few 2^-24 of the exact one
+    # relative to itself at any magnitude; the bound only keeps 1e-4 well above a float64 ulp of the coordinates)
+    assert max(np.abs(qx[ok]).max(), np.abs(qy[ok]).max(), np.abs(qz[ok]).max()) < 1e6
     pts = np.stack([qx[ok], qy[ok], qz[ok]], -1).astype(np.float64)
     cand = cKDTree(pts).query_pairs(float(link) * (1.0 + 1e-5) + 1e-4, output_type="ndarray")
     a, b = ok[cand[:, 0]], ok[cand[:, 1]]
