@@ -444,29 +444,32 @@ struct rsasa_context {
     size_t stream_sub_batches = 0; // a worker context of a stream of host batches: most sub-batches of a call (0: the default)
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
-    // rsasa_precompute_neighbors*: a workspace of their own (neighbors.cpp) - device batches in flight in ws[0] / ws[1] are
-    // neither waited for nor disturbed; the calls queue their work on `stream` behind whatever it holds
+    // rsasa_precompute_neighbors* and the point runs behind them - accessible points, exposure vectors, atom depth,
+    // surface components, contact counts, group contacts (neighbors.cpp).  A workspace of their own: device batches in
+    // flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls queue their work on `stream` behind whatever
+    // it holds.  What outlives a call is here: the workspace's and the cell array's sizes, the pinned block the device's
+    // verdicts come back in, and the lattice in the reference's order (the SASA path's cached lattices reorder the points
+    // above 128) with the point count it holds (0: none).
     Workspace nb_ws;
-    DeviceBuffer nb_x, nb_y, nb_z, nb_r, nb_id, nb_map, nb_counts, nb_offsets, nb_parts, nb_info, nb_entries, nb_spill, nb_recs;
-    PinnedBlock nb_host;           // the BatchStatus and NbInfo of the last neighbour call
+    PinnedBlock nb_host;
     uint64_t nb_cell_capacity = 0;
-    // rsasa_accessible_points*: the masks and values of the last call, and the lattice in the reference's order (the SASA
-    // path's cached lattices reorder the points above 128)
-    DeviceBuffer pt_masks, pt_sasa, pt_lattice;
-    size_t pt_lattice_points = 0;  // the point count pt_lattice holds (0: none)
-    // rsasa_exposure_vectors*: the sums and counts of the last call (the lists, lattice and values are the buffers above)
-    DeviceBuffer ex_vectors, ex_free;
-    // rsasa_atom_depth*: the nearest-dot keys and the exposed-point counts of the last call (the masks are pt_masks)
-    DeviceBuffer dp_keys, dp_free;
-    // rsasa_surface_components*: the dot offsets, the union-find forest and the labels of the last call (the masks are
-    // pt_masks, the exposed-point counts dp_free)
-    DeviceBuffer cc_offsets, cc_parent, cc_labels;
-    // rsasa_contact_points*: the per-entry counts of the last call (the lists, lattice and values are the buffers above)
-    DeviceBuffer ct_covered, ct_exclusive;
-    // rsasa_group_contacts*: the labels, the lists in label order with their own-group and row counts, the row offsets,
-    // and the rows and per-atom counts of the last call
-    DeviceBuffer gp_group, gp_sorted, gp_sorted_group, gp_own, gp_nrows, gp_offsets, gp_groups, gp_buried, gp_only, gp_self_free,
-        gp_free;
+    DeviceBuffer pt_lattice;
+    size_t pt_lattice_points = 0;
+    // The scratch of these calls.  Every one of them holds `mu` from its first line to its last and synchronises `stream`
+    // before it returns, so NOTHING here is live between calls: a call reserves what it uses (contents are not kept) and
+    // may find a buffer sized by another family.  Two members of one call never share a buffer; two families do.
+    struct RunScratch {
+        DeviceBuffer x, y, z, r, id, map;                                 // the uploaded columns and idx_map
+        DeviceBuffer counts, offsets, parts, info, entries, spill, recs;  // the neighbour lists (NbArgs)
+        DeviceBuffer masks, sasa;                                         // PtArgs::masks, ::sasa
+        DeviceBuffer free;         // accessible points per atom (exposure, depth, components, groups)
+        DeviceBuffer row_offsets;  // [N + 1]: where an atom's dots (components) or rows (groups) begin
+        DeviceBuffer vectors, keys;                                       // exposure sums; nearest-dot keys
+        DeviceBuffer parent, labels;                                      // union-find forest and labels, per dot
+        DeviceBuffer covered, exclusive;                                  // contact counts, per list entry
+        // group contacts: the labels, the lists in label order, own-group and row counts per atom, the rows
+        DeviceBuffer group, sorted, sorted_group, own, nrows, groups, buried, only, self_free;
+    } run;
 };
 
 namespace rsasa {

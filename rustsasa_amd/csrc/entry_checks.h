@@ -1,0 +1,66 @@
+// The argument rules of the neighbour-list and point-run entry points (neighbors.cpp), and the one description of their
+// input.  Plain host C++: no HIP, no context, nothing is written but N.  A rule returns the message of the first thing it
+// finds wrong, or null when the arguments stand; the entry points turn a message into RSASA_ERR_INVALID_ARGUMENT.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <cstdint>
+
+namespace rsasa {
+
+// The columns of a run in host memory: S structures, N atoms, structure s being atoms [so[s], so[s + 1]).
+struct Cols {
+    const float *x, *y, *z, *r;
+    const uint64_t *id;  // nullable
+    const uint32_t *so;
+    size_t S, N;
+    uint32_t one[2];  // `so` of a single structure
+    // a single structure of N atoms
+    Cols(const float *x, const float *y, const float *z, const float *r, const uint64_t *id, size_t N)
+        : x(x), y(y), z(z), r(r), id(id), so(one), S(1), N(N), one{0u, (uint32_t)N} {}
+    // the caller's structure_offsets, which check_offsets has passed and taken N from
+    Cols(const float *x, const float *y, const float *z, const float *r, const uint64_t *id, const uint32_t *so, size_t S, size_t N)
+        : x(x), y(y), z(z), r(r), id(id), so(so), S(S), N(N), one{} {}
+    Cols(const Cols &) = delete;  // (so may point into the object)
+    Cols &operator=(const Cols &) = delete;
+};
+
+// The shape of structure_offsets[0 .. n_structures]: non-decreasing from 0 to N, fewer than 2^31 - 1 atoms.
+inline const char *check_offsets(const uint32_t *so, size_t n_structures, size_t &N)
+{
+    N = 0;
+    if (!so) return "NULL argument";
+    if (n_structures >= 0x7FFFFFFFull) return "too many structures";
+    for (size_t s = 0; s < n_structures; s++)
+        if (so[s] > so[s + 1]) return "structure_offsets must be non-decreasing";
+    if (n_structures && so[0] != 0) return "structure_offsets[0] must be 0";
+    if (n_structures) N = so[n_structures];
+    if (N >= 0x7FFFFFFFull) return "more than 2^31 - 1 atoms";
+    return nullptr;
+}
+
+// The columns of N atoms.  rest: whatever else the call cannot do without is there - the caller's own test of the arrays
+// it needs always and of those that have an entry per atom (which may all be NULL when N is 0, as the columns may).
+inline const char *check_columns(size_t N, const float *x, const float *y, const float *z, const float *r, bool rest)
+{
+    if (!rest || (N && (!x || !y || !z || !r))) return "NULL argument";
+    if (N >= 0x7FFFFFFFull) return "more than 2^31 - 1 atoms";
+    return nullptr;
+}
+
+// check_columns, and the size of the lattice.
+inline const char *check_points(size_t N, const float *x, const float *y, const float *z, const float *r, bool rest,
+                                size_t n_points)
+{
+    if (n_points == 0 || n_points >= 0x7FFFFFFFull) return "n_points must be in [1, 2^31 - 1)";
+    return check_columns(N, x, y, z, r, rest);
+}
+
+// The link length of the surface components: finite and not negative (-0.0 is 0).
+inline const char *check_link(float link)
+{
+    if (!(link >= 0.0f) || std::isinf(link)) return "link must be finite and not negative";
+    return nullptr;
+}
+
+}  // namespace rsasa

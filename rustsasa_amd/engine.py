@@ -78,6 +78,9 @@ def _out_buffer(name, buf, n):
     return buf
 
 
+_SINGLE = object()  # in place of structure_offsets: the call goes to the single-structure entry point
+
+
 class Context:
     """One GPU, one HIP stream, one growable HBM workspace (rsasa_context_t)."""
 
@@ -209,25 +212,41 @@ class Context:
         while self._host_keepalive:
             self.host_batch_wait()
 
-    # ---- neighbour lists (precompute_neighbors, reference src/lib.rs:69-84) --
-    def _neighbor_call(self, call, n_lists: int):
-        """Runs `call(offsets, entries, capacity)` with a guessed capacity, and once more at the size the offsets give
-        when that was too small; returns (offsets uint64[n_lists + 1], entries NEIGHBOR_DTYPE[total])."""
-        offsets = np.zeros(n_lists + 1, np.uint64)
-        entries = np.empty(64 * n_lists, NEIGHBOR_DTYPE)
-        rc = call(offsets, entries, entries.shape[0])
-        if rc == _capi.RSASA_ERR_BUFFER_TOO_SMALL:
-            entries = np.empty(int(offsets[-1]), NEIGHBOR_DTYPE)
-            rc = call(offsets, entries, entries.shape[0])
-        self._check(rc)
-        return offsets, entries[:int(offsets[-1])]
+    # ---- neighbour lists and the point runs behind them: one private body per foo / foo_batch pair ----
+    def _entry(self, name, x, y, z, radius, ids, structure_offsets):
+        """The checked columns of a call of family `name`, and its C entry point with the context and the columns bound:
+        rsasa_<name> when structure_offsets is _SINGLE, else rsasa_<name>_batch.  The two signatures differ at one place
+        only, behind the columns (and the arguments `before`, if any): (n_atoms, *single) there, (ptr(so), n_struct)
+        here.  The other arguments follow."""
+        if structure_offsets is _SINGLE:
+            so = None
+            x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        else:
+            so = _offsets("structure_offsets", structure_offsets)
+            x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if so.shape[0] > 1 else 0)
 
-    def precompute_neighbors(self, x, y, z, radius, ids=None, probe_radius: float = 1.4,
-                             max_radius: Optional[float] = None, active_indices=None):
-        """rsasa_precompute_neighbors: the lists of the active atoms (all atoms when active_indices is None) in CSR form,
-        (offsets uint64[n_active + 1], entries NEIGHBOR_DTYPE[total]); each list sorted by (d^2, idx).  max_radius None:
-        the largest active radius (NaN radii skipped)."""
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
+        def call(*args, before=(), single=()):
+            fn = getattr(self._lib, "rsasa_" + name + ("" if so is None else "_batch"))
+            where = (x.shape[0], *single) if so is None else (ptr(so), so.shape[0] - 1)
+            return fn(self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), *before, *where, *args)
+        return (x, y, z, radius, ids), call
+
+    def _sized_call(self, call, n_lists: int, guess: int, *dtypes):
+        """Runs `call(offsets, *columns, capacity)` with columns of `guess` entries each, and once more at the size the
+        offsets give when that was too small; returns (offsets uint64[n_lists + 1], *columns cut to offsets[-1])."""
+        offsets = np.zeros(n_lists + 1, np.uint64)
+        cols = [np.empty(guess, dt) for dt in dtypes]
+        rc = call(offsets, *cols, guess)
+        if rc == _capi.RSASA_ERR_BUFFER_TOO_SMALL:
+            cols = [np.empty(int(offsets[-1]), dt) for dt in dtypes]
+            rc = call(offsets, *cols, cols[0].shape[0])
+        self._check(rc)
+        return (offsets,) + tuple(c[:int(offsets[-1])] for c in cols)
+
+    # ---- neighbour lists (precompute_neighbors, reference src/lib.rs:69-84) --
+    def _precompute_neighbors(self, x, y, z, radius, ids, probe_radius, max_radius, structure_offsets=_SINGLE,
+                              active_indices=None):
+        (x, *_), entry = self._entry("precompute_neighbors", x, y, z, radius, ids, structure_offsets)
         act = None
         if active_indices is not None:
             act = np.ascontiguousarray(active_indices, dtype=np.uint32)
@@ -237,25 +256,23 @@ class Context:
         mr = float("nan") if max_radius is None else float(max_radius)
 
         def call(offsets, entries, cap):
-            return self._lib.rsasa_precompute_neighbors(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], ptr(act),
-                0 if act is None else act.shape[0], probe_radius, mr, ptr(offsets), ptr(entries), cap)
-        return self._neighbor_call(call, n_lists)
+            # (single: the active atoms follow n_atoms in rsasa_precompute_neighbors; the batch call has none)
+            return entry(probe_radius, mr, ptr(offsets), ptr(entries), cap,
+                         single=(ptr(act), 0 if act is None else act.shape[0]))
+        return self._sized_call(call, n_lists, 64 * n_lists, NEIGHBOR_DTYPE)
+
+    def precompute_neighbors(self, x, y, z, radius, ids=None, probe_radius: float = 1.4,
+                             max_radius: Optional[float] = None, active_indices=None):
+        """rsasa_precompute_neighbors: the lists of the active atoms (all atoms when active_indices is None) in CSR form,
+        (offsets uint64[n_active + 1], entries NEIGHBOR_DTYPE[total]); each list sorted by (d^2, idx).  max_radius None:
+        the largest active radius (NaN radii skipped)."""
+        return self._precompute_neighbors(x, y, z, radius, ids, probe_radius, max_radius, active_indices=active_indices)
 
     def precompute_neighbors_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
                                    max_radius: Optional[float] = None):
         """rsasa_precompute_neighbors_batch: one grid per structure; (offsets uint64[n_atoms + 1] over the whole
         batch, entries NEIGHBOR_DTYPE[total]) with idx the index within the structure."""
-        so = _offsets("structure_offsets", structure_offsets)
-        n_struct = so.shape[0] - 1
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
-        mr = float("nan") if max_radius is None else float(max_radius)
-
-        def call(offsets, entries, cap):
-            return self._lib.rsasa_precompute_neighbors_batch(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, mr,
-                ptr(offsets), ptr(entries), cap)
-        return self._neighbor_call(call, x.shape[0])
+        return self._precompute_neighbors(x, y, z, radius, ids, probe_radius, max_radius, structure_offsets)
 
     def neighbor_lists(self, x, y, z, radius, ids=None, probe_radius: float = 1.4,
                        max_radius: Optional[float] = None, active_indices=None):
@@ -264,65 +281,58 @@ class Context:
         return [entries[int(offsets[i]):int(offsets[i + 1])] for i in range(offsets.shape[0] - 1)]
 
     # ---- accessible sphere points (the decisions behind each SASA value, reference src/lib.rs:96-223) ----
+    def _accessible_points(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("accessible_points", x, y, z, radius, ids, structure_offsets)
+        words = np.zeros((x.shape[0], _words(n_points)), np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(entry(probe_radius, n_points, ptr(words), ptr(sasa)))
+        return words, sasa
+
     def accessible_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
         """rsasa_accessible_points: (words uint32[N, (n_points + 31) // 32], sasa float32[N]); bit p & 31 of word p >> 5 of
         row i is 1 when point p of sphere_points(n_points) is accessible on atom i.  sasa equals calculate_sasa_soa."""
-        n_points = _n_points(n_points)
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
-        words = np.zeros((x.shape[0], _words(n_points)), np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-        self._check(self._lib.rsasa_accessible_points(
-            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, ptr(words),
-            ptr(sasa)))
-        return words, sasa
+        return self._accessible_points(x, y, z, radius, ids, probe_radius, n_points)
 
     def accessible_points_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
                                 n_points: int = 100):
         """rsasa_accessible_points_batch: accessible_points of every structure (one grid each), rows in batch order."""
-        n_points = _n_points(n_points)
-        so = _offsets("structure_offsets", structure_offsets)
-        n_struct = so.shape[0] - 1
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
-        words = np.zeros((x.shape[0], _words(n_points)), np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-        self._check(self._lib.rsasa_accessible_points_batch(
-            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
-            ptr(words), ptr(sasa)))
-        return words, sasa
+        return self._accessible_points(x, y, z, radius, ids, probe_radius, n_points, structure_offsets)
 
     # ---- exposure vectors (in which direction an atom is exposed: the sum of its accessible lattice points) ----
+    def _exposure_vectors(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("exposure_vectors", x, y, z, radius, ids, structure_offsets)
+        vectors = np.zeros((x.shape[0], 3), np.float32)
+        free = np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(entry(probe_radius, n_points, ptr(vectors), ptr(free), ptr(sasa)))
+        return vectors, free, sasa
+
     def exposure_vectors(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
         """rsasa_exposure_vectors: (vectors float32[N, 3], free uint32[N], sasa float32[N]).  vectors[i] is the float32 sum
         of the points of sphere_points(n_points) that are accessible on atom i, in the fixed order the header gives (a
         tree over each chunk of 64 points, the chunks ascending); free[i] their number, the popcount of
         accessible_points; sasa equals calculate_sasa_soa.  vectors[i] / free[i] is the mean outward direction;
         sas_volume() turns vectors and free into the volume the accessible surface encloses."""
-        n_points = _n_points(n_points)
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
-        vectors = np.zeros((x.shape[0], 3), np.float32)
-        free = np.zeros(x.shape[0], np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-        self._check(self._lib.rsasa_exposure_vectors(
-            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, ptr(vectors),
-            ptr(free), ptr(sasa)))
-        return vectors, free, sasa
+        return self._exposure_vectors(x, y, z, radius, ids, probe_radius, n_points)
 
     def exposure_vectors_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
                                n_points: int = 100):
         """rsasa_exposure_vectors_batch: exposure_vectors of every structure (one grid each), rows in batch order."""
-        n_points = _n_points(n_points)
-        so = _offsets("structure_offsets", structure_offsets)
-        n_struct = so.shape[0] - 1
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
-        vectors = np.zeros((x.shape[0], 3), np.float32)
-        free = np.zeros(x.shape[0], np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-        self._check(self._lib.rsasa_exposure_vectors_batch(
-            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
-            ptr(vectors), ptr(free), ptr(sasa)))
-        return vectors, free, sasa
+        return self._exposure_vectors(x, y, z, radius, ids, probe_radius, n_points, structure_offsets)
 
     # ---- atom depth (how far under the accessible surface an atom lies: its nearest accessible dot) ----
+    def _atom_depth(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("atom_depth", x, y, z, radius, ids, structure_offsets)
+        depth = np.zeros(x.shape[0], np.float32)
+        nearest = np.zeros(x.shape[0], np.uint32)
+        free = np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+        self._check(entry(probe_radius, n_points, ptr(depth), ptr(nearest), ptr(free), ptr(sasa)))
+        return depth, nearest, free, sasa
+
     def atom_depth(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
         """rsasa_atom_depth: (depth float32[N], nearest uint32[N], free uint32[N], sasa float32[N]).  depth[i] is the
         float32 distance from atom i's centre to the nearest dot of surface_points() of the structure's accessible
@@ -330,46 +340,23 @@ class Context:
         that owns that dot (ties: the smallest index); +inf and 0xFFFFFFFF where there is no such dot.  free[i] is the
         popcount of accessible_points, sasa equals calculate_sasa_soa.  depth - probe_radius estimates the distance to
         the molecular surface; residue_depth() averages depth over residues."""
-        n_points = _n_points(n_points)
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
-        depth = np.zeros(x.shape[0], np.float32)
-        nearest = np.zeros(x.shape[0], np.uint32)
-        free = np.zeros(x.shape[0], np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-        self._check(self._lib.rsasa_atom_depth(
-            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, ptr(depth),
-            ptr(nearest), ptr(free), ptr(sasa)))
-        return depth, nearest, free, sasa
+        return self._atom_depth(x, y, z, radius, ids, probe_radius, n_points)
 
     def atom_depth_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100):
         """rsasa_atom_depth_batch: atom_depth of every structure (one grid each, dots of other structures never count),
         rows in batch order; nearest holds indices within the atom's structure."""
-        n_points = _n_points(n_points)
-        so = _offsets("structure_offsets", structure_offsets)
-        n_struct = so.shape[0] - 1
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
-        depth = np.zeros(x.shape[0], np.float32)
-        nearest = np.zeros(x.shape[0], np.uint32)
-        free = np.zeros(x.shape[0], np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-        self._check(self._lib.rsasa_atom_depth_batch(
-            self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
-            ptr(depth), ptr(nearest), ptr(free), ptr(sasa)))
-        return depth, nearest, free, sasa
+        return self._atom_depth(x, y, z, radius, ids, probe_radius, n_points, structure_offsets)
 
     # ---- surface components (which connected piece of accessible surface a free point lies on) ----
-    def _component_call(self, call, n_atoms: int, n_points: int):
-        """The size-then-fill pattern of _contact_call for labels: call(dot_offsets, labels, capacity) with a guessed
-        capacity, and once more at dot_offsets[-1] labels when that was too small; returns (dot_offsets uint64[N + 1],
-        labels uint32[dots])."""
-        offsets = np.zeros(n_atoms + 1, np.uint64)
-        labels = np.empty(min(n_points, 32) * n_atoms, np.uint32)
-        rc = call(offsets, labels, labels.shape[0])
-        if rc == _capi.RSASA_ERR_BUFFER_TOO_SMALL:
-            labels = np.empty(int(offsets[-1]), np.uint32)
-            rc = call(offsets, labels, labels.shape[0])
-        self._check(rc)
-        return offsets, labels[:int(offsets[-1])]
+    def _surface_components(self, x, y, z, radius, ids, probe_radius, n_points, link, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, _, _, radius, _), entry = self._entry("surface_components", x, y, z, radius, ids, structure_offsets)
+        link = default_link(radius, probe_radius, n_points) if link is None else link
+        free, sasa = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, labels, cap):
+            return entry(probe_radius, n_points, link, ptr(offsets), ptr(labels), cap, ptr(free), ptr(sasa))
+        return self._sized_call(call, x.shape[0], min(n_points, 32) * x.shape[0], np.uint32) + (free, sasa)
 
     def surface_components(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, link=None):
         """rsasa_surface_components: (dot_offsets uint64[N + 1], labels uint32[dots], free uint32[N], sasa float32[N]).
@@ -379,16 +366,7 @@ class Context:
         link None: default_link(radius, probe_radius, n_points).  free is the popcount of accessible_points, sasa
         equals calculate_sasa_soa.  component_table() ranks the components, split_sasa() splits each atom's area into
         the largest component's and the rest."""
-        n_points = _n_points(n_points)
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
-        link = default_link(radius, probe_radius, n_points) if link is None else link
-        free, sasa = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.float32)
-
-        def call(offsets, labels, cap):
-            return self._lib.rsasa_surface_components(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points, link,
-                ptr(offsets), ptr(labels), cap, ptr(free), ptr(sasa))
-        return self._component_call(call, x.shape[0], n_points) + (free, sasa)
+        return self._surface_components(x, y, z, radius, ids, probe_radius, n_points, link)
 
     def surface_components_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
                                  n_points: int = 100, link=None):
@@ -396,31 +374,17 @@ class Context:
         structures are never linked).  dot_offsets runs over the whole batch; labels are dot numbers within the
         structure (subtract dot_offsets[structure_offsets[s]] from a position to get one).  link None: default_link of
         the whole batch's radii."""
-        n_points = _n_points(n_points)
-        so = _offsets("structure_offsets", structure_offsets)
-        n_struct = so.shape[0] - 1
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
-        link = default_link(radius, probe_radius, n_points) if link is None else link
-        free, sasa = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.float32)
-
-        def call(offsets, labels, cap):
-            return self._lib.rsasa_surface_components_batch(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points, link,
-                ptr(offsets), ptr(labels), cap, ptr(free), ptr(sasa))
-        return self._component_call(call, x.shape[0], n_points) + (free, sasa)
+        return self._surface_components(x, y, z, radius, ids, probe_radius, n_points, link, structure_offsets)
 
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
-    def _contact_call(self, call, n_atoms: int):
-        """_neighbor_call with the two count columns beside the entries: call(offsets, entries, covered, exclusive,
-        capacity); returns (offsets, entries, covered uint32[total], exclusive uint32[total])."""
-        counts = []
+    def _contact_points(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("contact_points", x, y, z, radius, ids, structure_offsets)
+        sasa = np.zeros(x.shape[0], np.float32)
 
-        def sized(offsets, entries, cap):
-            counts[:] = [np.empty(cap, np.uint32), np.empty(cap, np.uint32)]
-            return call(offsets, entries, counts[0], counts[1], cap)
-        offsets, entries = self._neighbor_call(sized, n_atoms)
-        total = entries.shape[0]
-        return offsets, entries, counts[0][:total], counts[1][:total]
+        def call(offsets, entries, covered, exclusive, cap):
+            return entry(probe_radius, n_points, ptr(offsets), ptr(entries), ptr(covered), ptr(exclusive), cap, ptr(sasa))
+        return self._sized_call(call, x.shape[0], 64 * x.shape[0], NEIGHBOR_DTYPE, np.uint32, np.uint32) + (sasa,)
 
     def contact_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
         """rsasa_contact_points: (offsets uint64[N + 1], entries NEIGHBOR_DTYPE[total], covered uint32[total],
@@ -428,46 +392,27 @@ class Context:
         entry e of atom i's list, covered[e] counts the points of sphere_points(n_points) on atom i that the entry
         occludes, exclusive[e] those that no other entry of the list occludes.  sasa equals calculate_sasa_soa;
         contact_areas() turns counts into A^2."""
-        n_points = _n_points(n_points)
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
-        sasa = np.zeros(x.shape[0], np.float32)
-
-        def call(offsets, entries, covered, exclusive, cap):
-            return self._lib.rsasa_contact_points(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), x.shape[0], probe_radius, n_points,
-                ptr(offsets), ptr(entries), ptr(covered), ptr(exclusive), cap, ptr(sasa))
-        return self._contact_call(call, x.shape[0]) + (sasa,)
+        return self._contact_points(x, y, z, radius, ids, probe_radius, n_points)
 
     def contact_points_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
                              n_points: int = 100):
         """rsasa_contact_points_batch: contact_points of every structure (one grid each); offsets over the whole batch,
         idx the index within the structure."""
-        n_points = _n_points(n_points)
-        so = _offsets("structure_offsets", structure_offsets)
-        n_struct = so.shape[0] - 1
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
-        sasa = np.zeros(x.shape[0], np.float32)
-
-        def call(offsets, entries, covered, exclusive, cap):
-            return self._lib.rsasa_contact_points_batch(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(so), n_struct, probe_radius, n_points,
-                ptr(offsets), ptr(entries), ptr(covered), ptr(exclusive), cap, ptr(sasa))
-        return self._contact_call(call, x.shape[0]) + (sasa,)
+        return self._contact_points(x, y, z, radius, ids, probe_radius, n_points, structure_offsets)
 
     # ---- group contacts (which partner group buries which points: unions of the same tests over a label's entries) ----
-    def _group_call(self, call, n_atoms: int):
-        """The size-then-fill pattern of _contact_call for rows: call(offsets, groups, buried, only, capacity) with a
-        guessed capacity, and once more at offsets[-1] rows when that was too small; returns (offsets uint64[N + 1],
-        partner_groups uint32[rows], buried uint32[rows], only uint32[rows])."""
-        offsets = np.zeros(n_atoms + 1, np.uint64)
-        cols = [np.empty(16 * n_atoms, np.uint32) for _ in range(3)]
-        rc = call(offsets, *cols, cols[0].shape[0])
-        if rc == _capi.RSASA_ERR_BUFFER_TOO_SMALL:
-            cols = [np.empty(int(offsets[-1]), np.uint32) for _ in range(3)]
-            rc = call(offsets, *cols, cols[0].shape[0])
-        self._check(rc)
-        rows = int(offsets[-1])
-        return (offsets,) + tuple(c[:rows] for c in cols)
+    def _group_contacts(self, x, y, z, radius, ids, groups, probe_radius, n_points, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("group_contacts", x, y, z, radius, ids, structure_offsets)
+        groups = _labels(groups, x.shape[0])
+        self_free, free = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.uint32)
+        sasa = np.zeros(x.shape[0], np.float32)
+
+        def call(offsets, partner, buried, only, cap):
+            # (before: the labels sit between the columns and n_atoms / structure_offsets in both signatures)
+            return entry(probe_radius, n_points, ptr(offsets), ptr(partner), ptr(buried), ptr(only), cap, ptr(self_free),
+                         ptr(free), ptr(sasa), before=(ptr(groups),))
+        return self._sized_call(call, x.shape[0], 16 * x.shape[0], np.uint32, np.uint32, np.uint32) + (self_free, free, sasa)
 
     def group_contacts(self, x, y, z, radius, ids, groups, probe_radius: float = 1.4, n_points: int = 100):
         """rsasa_group_contacts: (offsets uint64[N + 1], partner_groups uint32[rows], buried uint32[rows],
@@ -477,35 +422,13 @@ class Context:
         group leaves free (self_free of them), only = those no other foreign label occludes; free = the accessible
         points in the whole structure, sasa equals calculate_sasa_soa.  group_areas() sums rows into a group x group
         table of A^2."""
-        n_points = _n_points(n_points)
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids)
-        groups = _labels(groups, x.shape[0])
-        self_free, free = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-
-        def call(offsets, partner, buried, only, cap):
-            return self._lib.rsasa_group_contacts(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(groups), x.shape[0], probe_radius, n_points,
-                ptr(offsets), ptr(partner), ptr(buried), ptr(only), cap, ptr(self_free), ptr(free), ptr(sasa))
-        return self._group_call(call, x.shape[0]) + (self_free, free, sasa)
+        return self._group_contacts(x, y, z, radius, ids, groups, probe_radius, n_points)
 
     def group_contacts_batch(self, x, y, z, radius, ids, groups, structure_offsets, probe_radius: float = 1.4,
                              n_points: int = 100):
         """rsasa_group_contacts_batch: group_contacts of every structure (one grid each), offsets over the whole batch;
         labels are compared within a structure only, so their values may be reused from one structure to the next."""
-        n_points = _n_points(n_points)
-        so = _offsets("structure_offsets", structure_offsets)
-        n_struct = so.shape[0] - 1
-        x, y, z, radius, ids = _columns(x, y, z, radius, ids, int(so[-1]) if n_struct else 0)
-        groups = _labels(groups, x.shape[0])
-        self_free, free = np.zeros(x.shape[0], np.uint32), np.zeros(x.shape[0], np.uint32)
-        sasa = np.zeros(x.shape[0], np.float32)
-
-        def call(offsets, partner, buried, only, cap):
-            return self._lib.rsasa_group_contacts_batch(
-                self._h, ptr(x), ptr(y), ptr(z), ptr(radius), ptr(ids), ptr(groups), ptr(so), n_struct, probe_radius,
-                n_points, ptr(offsets), ptr(partner), ptr(buried), ptr(only), cap, ptr(self_free), ptr(free), ptr(sasa))
-        return self._group_call(call, x.shape[0]) + (self_free, free, sasa)
+        return self._group_contacts(x, y, z, radius, ids, groups, probe_radius, n_points, structure_offsets)
 
     def surface_points(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100):
         """The accessible points themselves: (atom_index uint32[M], xyz float32[M, 3]), see surface_points()."""

@@ -1,0 +1,153 @@
+"""The seven families that share one host prologue and one set of scratch buffers (neighbors.cpp: neighbour lists,
+accessible points, exposure vectors, atom depth, surface components, contact counts, group contacts), walked in an order
+that makes every shared buffer grow, be reused while oversized, and serve another family than the one that sized it.
+What the per-family suites cannot see: a first call on a fresh context whose every list is empty (no fill has ever run,
+the entries' buffer does not exist yet), and a result that depends on which family ran before.
+
+Inputs: A one atom (its list is empty), B the 1jcd fixture, C a batch of A, an empty structure and B.  Every result of
+the walk is compared byte for byte with the same call on a context that made no other call; B is also compared with the
+Python models (points, depth, components), so the comparison is not only the library against itself."""
+import functools
+
+import numpy as np
+import pytest
+
+import components_model as cm
+import depth_model as dm
+import exposure_model as em
+import nb_helpers as nh
+import points_model as pm
+
+pytestmark = pytest.mark.gpu
+
+PROBE = 1.4
+N_POINTS = (100, 129)  # 4 mask words, 4 points past the fused 96; 5 words, the last holding the one point past the fused 128
+ORDER = ("points", "groups", "depth", "contacts", "components", "exposure", "neighbours")
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs():
+    """{name: (x, y, z, r, ids, groups, structure_offsets or None)}."""
+    bx, by, bz, br, bids = nh.protor("1jcd.pdb")
+    n = len(bx)
+    bgroups = (np.arange(n, dtype=np.int64) * 3 // n).astype(np.uint32)
+    f = lambda *v: np.array(v, np.float32)  # noqa: E731
+    a = (f(1.0), f(-2.0), f(3.0), f(1.7), np.array([7], np.uint64), np.array([0], np.uint32), None)
+    b = (bx, by, bz, br, bids, bgroups, None)
+    c = tuple(np.concatenate([p, q]) for p, q in zip(a[:6], b[:6])) + (np.array([0, 1, 1, 1 + n], np.uint32),)
+    return {"A": a, "B": b, "C": c}
+
+
+def _link(r, n_points):
+    import rustsasa_amd
+    return rustsasa_amd.default_link(r, PROBE, n_points)
+
+
+def _call(ctx, family, inp, n_points):
+    """The family's call on `inp` (the single-structure method, or the batch method when the input has offsets) as a
+    tuple of arrays."""
+    x, y, z, r, ids, groups, so = inp
+    batch = so is not None
+    cols = (x, y, z, r, ids)
+    if family == "neighbours":
+        return ctx.precompute_neighbors_batch(*cols, so, PROBE) if batch else ctx.precompute_neighbors(*cols, PROBE)
+    if family == "groups":
+        tail = (PROBE, n_points)
+        return ctx.group_contacts_batch(*cols, groups, so, *tail) if batch else ctx.group_contacts(*cols, groups, *tail)
+    if family == "components":
+        tail = (PROBE, n_points, _link(r, n_points))
+        return ctx.surface_components_batch(*cols, so, *tail) if batch else ctx.surface_components(*cols, *tail)
+    single, many = {"points": (ctx.accessible_points, ctx.accessible_points_batch),
+                    "depth": (ctx.atom_depth, ctx.atom_depth_batch),
+                    "contacts": (ctx.contact_points, ctx.contact_points_batch),
+                    "exposure": (ctx.exposure_vectors, ctx.exposure_vectors_batch)}[family]
+    return many(*cols, so, PROBE, n_points) if batch else single(*cols, PROBE, n_points)
+
+
+def _alone(family, name, n_points):
+    """The call on a context that makes no other call."""
+    import rustsasa_amd
+    with rustsasa_amd.Context(0) as ctx:
+        return _call(ctx, family, _inputs()[name], n_points)
+
+
+def _same(got, want):
+    return len(got) == len(want) and all(
+        g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes() for g, w in zip(got, want))
+
+
+@pytest.fixture(scope="module")
+def alone():
+    """{(family, input, n_points): the result on a fresh context}, computed once and left unchanged."""
+    return {(f, i, n): _alone(f, i, n) for n in N_POINTS for f in ORDER for i in _inputs()}
+
+
+# ---- fresh contexts: the first call has nothing but empty lists ---------------------------------------------------
+
+@pytest.mark.parametrize("family", ORDER)
+def test_first_call_on_a_fresh_context_has_only_empty_lists(alone, family):
+    n_points = 100
+    x, y, z, r, ids, groups, _ = _inputs()["A"]
+    got = alone[(family, "A", n_points)]  # (raises unless the call returned RSASA_OK)
+    full = pm.pack(np.ones((1, n_points), bool))
+    sasa = pm.sasa_of(r, PROBE, np.array([n_points]), n_points)
+    none = np.zeros(2, np.uint64)
+    if family == "neighbours":
+        offsets, entries = got
+        assert np.array_equal(offsets, none) and entries.shape == (0,)
+        return
+    assert got[-1].tobytes() == sasa.tobytes()
+    if family == "points":
+        assert np.array_equal(got[0], full)  # every point accessible
+    elif family == "exposure":
+        vectors, free, _ = got
+        want = em.vectors_of(np.ones((1, n_points), bool), n_points)  # every lattice point, in the kernel's fixed order
+        assert free.tolist() == [n_points] and vectors.dtype == want.dtype and vectors.tobytes() == want.tobytes()
+    elif family == "contacts":
+        offsets, entries, covered, exclusive, _ = got
+        assert np.array_equal(offsets, none) and entries.shape == covered.shape == exclusive.shape == (0,)
+    elif family == "groups":
+        offsets, partner, buried, only, self_free, free, _ = got
+        assert np.array_equal(offsets, none) and partner.shape == buried.shape == only.shape == (0,)
+        assert self_free.tolist() == [n_points] and free.tolist() == [n_points]
+    elif family == "depth":
+        depth, nearest, free, _ = got
+        want_depth, want_nearest, _ = dm.atom_depth(x, y, z, r, ids, PROBE, n_points, mask=np.ones((1, n_points), bool))
+        assert free.tolist() == [n_points] and nearest.tolist() == [0] and want_nearest.tolist() == [0]
+        assert depth.tobytes() == want_depth.tobytes()  # the atom's own nearest dot
+    else:
+        offsets, labels, free, _ = got
+        want_off, want_labels, _ = cm.components(x, y, z, r, ids, PROBE, n_points, _link(r, n_points),
+                                                 mask=np.ones((1, n_points), bool))
+        assert free.tolist() == [n_points] and np.array_equal(offsets, want_off) and np.array_equal(labels, want_labels)
+
+
+# ---- the walk: one context through every family and back -----------------------------------------------------------
+
+@pytest.mark.parametrize("n_points", N_POINTS)
+def test_walk_through_the_families_and_back(alone, n_points):
+    import rustsasa_amd
+    with rustsasa_amd.Context(0) as ctx:
+        for step, family in enumerate(ORDER + ORDER[::-1]):
+            for name in ("B", "A", "C"):  # grows the buffers, reuses them oversized, then a batch
+                got = _call(ctx, family, _inputs()[name], n_points)
+                assert _same(got, alone[(family, name, n_points)]), (step, family, name)
+
+
+# ---- input B against the models ---------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n_points", N_POINTS)
+def test_fixture_equals_the_models(alone, n_points):
+    x, y, z, r, ids, _, _ = _inputs()["B"]
+    mask = pm.exposed_masks(x, y, z, r, ids, PROBE, n_points, 8)
+    free_want = mask.sum(axis=1).astype(np.uint32)
+    words, sasa = alone[("points", "B", n_points)]
+    assert np.array_equal(words, pm.pack(mask))
+    assert sasa.tobytes() == pm.sasa_of(r, PROBE, free_want, n_points).tobytes()
+    depth, nearest, free, _ = alone[("depth", "B", n_points)]
+    want_depth, want_nearest, _ = dm.atom_depth(x, y, z, r, ids, PROBE, n_points, mask=mask)
+    assert np.array_equal(free, free_want) and np.array_equal(nearest, want_nearest)
+    assert depth.tobytes() == want_depth.tobytes()
+    offsets, labels, free, _ = alone[("components", "B", n_points)]
+    want_off, want_labels, _ = cm.components(x, y, z, r, ids, PROBE, n_points, _link(r, n_points), mask=mask)
+    assert np.array_equal(free, free_want) and np.array_equal(offsets, want_off) and np.array_equal(labels, want_labels)
