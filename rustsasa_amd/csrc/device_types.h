@@ -228,7 +228,7 @@ struct ExArgs {
 // accessible dots of its structure.
 struct DpArgs {
     PtArgs p;                           // p.masks, p.words: the masks k_accessible_points wrote; p.sasa as there
-    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_depth_free)
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_mask_free)
     unsigned long long *keys;           // [n_atoms], input order: min of (float bits of d2) << 32 | index within the structure of
                                         // the dot's owner, over the accessible dots of the atom's structure whose d2 is no NaN
                                         // (the definition: include/rustsasa_amd.h); all ones where there is none
@@ -239,7 +239,7 @@ struct DpArgs {
 // batch in (atom, point) order and, per dot, the smallest dot of its connected component.
 struct CcArgs {
     PtArgs p;                           // p.masks, p.words: the masks k_accessible_points wrote; p.sasa as there
-    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_component_free)
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_mask_free)
     const unsigned long long *dot_offsets;  // [n_atoms + 1] exclusive scan of free: atom i's dots are [dot_offsets[i], dot_offsets[i + 1])
     unsigned long long n_dots;          // dot_offsets[n_atoms], below 2^32
     uint32_t *parent;                   // [n_dots] the union-find forest: parent <= self, a root is the smallest dot of its tree
@@ -334,11 +334,11 @@ void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t str
 void launch_accessible_points(const PtArgs &a, hipStream_t stream);
 // The exposed-point sums and counts (points.hip) from those lists.
 void launch_exposure_vectors(const ExArgs &e, hipStream_t stream);
-// The exposed-point counts and the nearest-dot keys (depth.hip) from the masks launch_accessible_points wrote.
+// The exposed-point counts (points.hip) from the masks launch_accessible_points wrote: free[n_atoms], input order.
+void launch_mask_free(const PtArgs &a, uint32_t *free, hipStream_t stream);
+// The nearest-dot keys (depth.hip) from those masks and counts (DpArgs::free).
 void launch_atom_depth(const DpArgs &d, hipStream_t stream);
-// The exposed-point counts (components.hip) from the masks launch_accessible_points wrote; then, with CcArgs::dot_offsets,
-// the component labels of the dots.
-void launch_component_free(const CcArgs &c, hipStream_t stream);
+// The component labels of the dots (components.hip) from those masks and counts, with CcArgs::dot_offsets.
 void launch_components(const CcArgs &c, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);

@@ -30,6 +30,12 @@ __device__ __forceinline__ uint32_t f2u_sat(float v)
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & (kWave - 1); }
 __device__ __forceinline__ unsigned long long ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
+// The set bits of m below this lane's: the lane's slot when the lanes of m are compacted in lane order.
+__device__ __forceinline__ uint32_t mbcnt64(unsigned long long m)
+{
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+
 // Orders this wave's LDS writes before its later LDS reads (same wave only).
 __device__ __forceinline__ void wave_lds_fence()
 {

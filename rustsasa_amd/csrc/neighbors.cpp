@@ -271,7 +271,7 @@ int ex_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, floa
 
 // ---- atom depth (rsasa_atom_depth*) ----
 
-// One run of the atom depths: pt_run's masks stay on the device; k_depth_free counts them and k_atom_depth searches the
+// One run of the atom depths: pt_run's masks stay on the device; k_mask_free counts them and k_atom_depth searches the
 // grid for every atom's nearest accessible dot.  8 bytes per atom come back (and 4 each for the counts and the values,
 // if asked); the square root of the key's d2 is taken here (sqrtf: correctly rounded).
 int dp_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, float *out_depth, uint32_t *out_nearest,
@@ -291,6 +291,7 @@ int dp_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, floa
     d.keys = (unsigned long long *)R.keys.p;
     hipStream_t st = ctx->stream;
     launch_accessible_points(d.p, st);
+    launch_mask_free(d.p, d.free, st);
     launch_atom_depth(d, st);
     RS_HIP(ctx, hipGetLastError());
     std::vector<uint64_t> keys(c.N);
@@ -311,7 +312,7 @@ int dp_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, floa
 
 // ---- surface components (rsasa_surface_components*) ----
 
-// One run of the surface components: pt_run's masks stay on the device; k_component_free counts them, the scan of the
+// One run of the surface components: pt_run's masks stay on the device; k_mask_free counts them, the scan of the
 // neighbour counts turns the counts into out_offsets, the caller's label buffer is checked against out_offsets[N] as
 // nb_run checks its entries, and the union-find kernels label the dots.  8 bytes per atom and 4 per dot come back (and
 // 4 per atom each for the counts and the values, if asked).
@@ -337,7 +338,7 @@ int cc_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, floa
     cc.link2 = link * link;
     hipStream_t st = ctx->stream;
     launch_accessible_points(cc.p, st);
-    launch_component_free(cc, st);
+    launch_mask_free(cc.p, cc.free, st);
     NbArgs scan = l.a;  // (the neighbour run has read its parts and its info)
     scan.counts = cc.free;
     scan.offsets = (unsigned long long *)R.row_offsets.p;

@@ -53,13 +53,6 @@ struct OccArgs {
 };
 
 #include "occlusion_v0.inc"
-
-__device__ __forceinline__ uint32_t mbcnt64(unsigned long long m)
-{
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-
 #include "occlusion_v3.inc"
 #include "occlusion_fast.inc"
 #include "occlusion_mx.inc"

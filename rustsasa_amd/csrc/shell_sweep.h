@@ -1,0 +1,149 @@
+// The shell sweep that k_atom_depth (depth.hip) and k_component_link (components.hip) share (device only, gfx950 only).
+// One wave per cell-sorted atom i.  The cells of its structure's grid are swept in Chebyshev shells s = 0, 1, 2, ... around
+// its own cell: shell s is the cells at distance exactly s, cut into x-runs of cell starts as nb_runs cuts the 5x5x5 block
+// - a row (y, z) on the rim of the shell's square gives the whole run [cx - s, cx + s], a row inside it the two cells
+// cx - s and cx + s -, 64 rows at a time (sh_step_runs), both cell-start encodings (StructGrid::in_lds).  Lanes then go
+// over the atoms of the runs, 64 at a time (sh_pos), and the atoms the caller keeps are compacted into LDS (sh_stage;
+// k_component_link writes that one step out, see there).
+//
+// What an unseen atom implies.  Let h = StructGrid::cell_size = probe + max_r.  After shell s every atom j not yet seen
+// has a cell coordinate that differs from i's by more than s along some axis.  A cell coordinate is floor(t'), t' the
+// float32 value of (x - min) * inv_cell, except where the clamp to dim - 1 lowered it; following the cases (i clamped: no
+// larger coordinate exists; j clamped: its coordinate is the largest, so it is not below i's) |t'_j - t'_i| > s.  In a
+// structure that passes sh_margins_hold - no odd radius or coordinate (every 0 <= R_j <= h, R_j and h being the same
+// rounded sum of a radius and the probe), probe >= 0, and every |coordinate| <= 65536 h - a coordinate's ulp is at most
+// h / 128 and t' < 2^18, so t' is within 1/16 of the exact (x - min) / h, and |x_j - x_i| > (s - 1/8) h.  Every dot of j
+// lies within R_j <= h of c_j, and a dot q = c_j + R_j * s_k and a difference of two points carry a few roundings of at
+// most h / 128 each.  The stop rule of k_atom_depth and the reach of k_component_link follow from this; without the
+// margins both sweep until the shells cover the grid (ShCell::s_last), which is always exact.
+#pragma once
+#include "device_utils.h"
+
+namespace rsasa {
+namespace {
+
+constexpr uint32_t kShRuns = 128;  // x-runs of one step: two per row, 64 rows
+
+// Whether the margins hold in this structure (see the head of the file).  NaN bounds fail every comparison.
+__device__ __forceinline__ bool sh_margins_hold(const StructGrid &g, float probe)
+{
+    const float h = g.cell_size;
+    const float ax = fabsf(g.min_x) + (float)g.dim_x * h, ay = fabsf(g.min_y) + (float)g.dim_y * h,
+                az = fabsf(g.min_z) + (float)g.dim_z * h;
+    return (g.odd_radii & 1u) == 0u && probe >= 0.0f && h > 0.0f && fmaxf(ax, fmaxf(ay, az)) <= 65536.0f * h;
+}
+
+// Flat position f of the concatenated runs -> cell-sorted position (nb_pos over kShRuns entries).
+__device__ __forceinline__ uint32_t sh_pos(const uint32_t *s_excl, const uint32_t *s_start, uint32_t f)
+{
+    uint32_t lo = 0;
+#pragma unroll
+    for (int step = kShRuns / 2; step > 0; step >>= 1)
+        if (s_excl[lo + step] <= f) lo += step;
+    return s_start[lo] + (f - s_excl[lo]);
+}
+
+struct ShCell {  // the cell of the wave's atom
+    uint32_t cx, cy, cz;
+    uint32_t s_last;    // the last shell that holds a cell of the grid
+    bool rel16;         // the structure's cell starts are 16-bit, relative to pos_base
+    uint32_t pos_base;
+};
+
+__device__ __forceinline__ ShCell sh_cell(const StructGrid &g, const float4 me)
+{
+    ShCell c;
+    c.rel16 = g.in_lds != 0u;
+    c.pos_base = c.rel16 ? g.sorted_base : 0u;
+    cell_coords(g, me.x, me.y, me.z, c.cx, c.cy, c.cz);
+    c.s_last = max(max(max(c.cx, g.dim_x - 1u - c.cx), max(c.cy, g.dim_y - 1u - c.cy)), max(c.cz, g.dim_z - 1u - c.cz));
+    return c;
+}
+
+struct ShShell {  // shell s: the rows (y, z) of its square that lie in the grid, row r = (y0 + r % ny, z0 + r / ny)
+    uint32_t y0, z0, ny;
+    unsigned long long n_rows;
+    uint32_t x0, x1;      // the x-run of a row on the rim
+    bool has_lo, has_hi;  // the cells cx - s, cx + s exist
+};
+
+__device__ __forceinline__ ShShell sh_shell(const StructGrid &g, const ShCell &c, uint32_t s)
+{
+    ShShell sh;
+    const uint32_t y1 = min(c.cy + s, g.dim_y - 1u), z1 = min(c.cz + s, g.dim_z - 1u);
+    sh.y0 = c.cy >= s ? c.cy - s : 0u;
+    sh.z0 = c.cz >= s ? c.cz - s : 0u;
+    sh.ny = y1 - sh.y0 + 1u;
+    sh.n_rows = (unsigned long long)sh.ny * (z1 - sh.z0 + 1u);
+    sh.x0 = c.cx >= s ? c.cx - s : 0u;
+    sh.x1 = min(c.cx + s, g.dim_x - 1u);
+    sh.has_lo = c.cx >= s;
+    sh.has_hi = c.cx + s <= g.dim_x - 1u;
+    return sh;
+}
+
+// One step of shell s: lane l turns row r0 + l into its x-runs, and the wave's 128 runs go to s_excl (the exclusive
+// prefix sums of their lengths) and s_start (their first cell-sorted positions).  Returns the atoms of the step.  (An empty
+// run shares its prefix with the next one; sh_pos then lands on the last run of that prefix, which is the one that holds
+// the position.)
+__device__ __forceinline__ uint32_t sh_step_runs(const BatchView &b, const StructGrid &g, const ShCell &c, const ShShell &sh,
+                                                 uint32_t s, unsigned long long r0, uint32_t *s_excl, uint32_t *s_start)
+{
+    const uint32_t lane = lane_id();
+    uint32_t len_a = 0, len_b = 0, start_a = 0, start_b = 0;
+    const unsigned long long rr = r0 + lane;
+    if (rr < sh.n_rows) {
+        const uint32_t yy = sh.y0 + (uint32_t)(rr % sh.ny), zz = sh.z0 + (uint32_t)(rr / sh.ny);
+        const uint32_t dy = yy > c.cy ? yy - c.cy : c.cy - yy, dz = zz > c.cz ? zz - c.cz : c.cz - zz;
+        const uint32_t c_row = g.cell_base + yy * g.dim_x + zz * g.dim_x * g.dim_y;
+        if (max(dy, dz) == s) {  // on the rim: every cell of [x0, x1] is at distance s
+            uint32_t f0, f1;
+            load_cell_start2(b.cells, c_row + sh.x0, c_row + sh.x1 + 1u, c.rel16, f0, f1);
+            start_a = c.pos_base + f0;
+            len_a = f1 - f0;
+        } else {  // inside (s >= 1): the two cells at |dx| = s
+            if (sh.has_lo) {
+                uint32_t f0, f1;
+                load_cell_start2(b.cells, c_row + c.cx - s, c_row + c.cx - s + 1u, c.rel16, f0, f1);
+                start_a = c.pos_base + f0;
+                len_a = f1 - f0;
+            }
+            if (sh.has_hi) {
+                uint32_t f0, f1;
+                load_cell_start2(b.cells, c_row + c.cx + s, c_row + c.cx + s + 1u, c.rel16, f0, f1);
+                start_b = c.pos_base + f0;
+                len_b = f1 - f0;
+            }
+        }
+    }
+    const uint32_t incl = wave_incl_scan(len_a + len_b);
+    wave_lds_fence();  // (every lane is done with the previous step's runs)
+    s_excl[2u * lane] = incl - len_a - len_b;
+    s_excl[2u * lane + 1u] = incl - len_b;
+    s_start[2u * lane] = start_a;
+    s_start[2u * lane + 1u] = start_b;
+    wave_lds_fence();
+    return wave_bcast(incl, kWave - 1);
+}
+
+// The lanes with `keep` (their atom at cell-sorted position q) are compacted into LDS in lane order: s_atom gets
+// (c_j, R_j = r_j + probe), s_who the caller's pair.  Returns the number staged (the same in every lane); 0: nothing was
+// written.
+__device__ __forceinline__ uint32_t sh_stage(const BatchView &b, bool keep, uint32_t q, uint2 who, float4 *s_atom, uint2 *s_who)
+{
+    const unsigned long long m = ballot64(keep);
+    if (m == 0ull) return 0u;
+    const uint32_t n_staged = (uint32_t)__popcll(m);
+    const uint32_t slot = mbcnt64(m);
+    wave_lds_fence();  // (every lane is done with the previous atoms)
+    if (keep) {
+        const float4 o = b.sorted_xyzr[q];
+        s_atom[slot] = make_float4(o.x, o.y, o.z, o.w + b.probe);
+        s_who[slot] = who;
+    }
+    wave_lds_fence();
+    return n_staged;
+}
+
+}  // namespace
+}  // namespace rsasa

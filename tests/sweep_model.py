@@ -38,7 +38,7 @@ def odd_input(x, y, z, r):
 
 
 def margin_sums(x, y, z, r, probe):
-    """(float32[3], float32): fabsf(min) + (float)dim * h per axis and 65536 h, as dp_margins_hold forms them."""
+    """(float32[3], float32): fabsf(min) + (float)dim * h per axis and 65536 h, as sh_margins_hold forms them."""
     mn, _, dims = tc.grid_of(x, y, z, r, probe)
     h = F(probe) + np.max(r)
     a = np.array([np.abs(mn[k]) + F(dims[k]) * h for k in range(3)], F)
@@ -46,7 +46,7 @@ def margin_sums(x, y, z, r, probe):
 
 
 def margins_hold(x, y, z, r, probe):
-    """dp_margins_hold / cc_margins_hold restated in float32 for one structure (not empty)."""
+    """sh_margins_hold (shell_sweep.h) restated in float32 for one structure (not empty)."""
     x, y, z, r = (np.ascontiguousarray(a, F) for a in (x, y, z, r))
     if odd_input(x, y, z, r):
         return False
@@ -122,7 +122,7 @@ def shell_steps(g, i, s, drop_lo=False, drop_hi=False, rows_first_step_only=Fals
         run_len = np.stack([len_a[sl], len_b[sl]], -1).ravel()
         excl = np.cumsum(run_len) - run_len
         total = int(run_len.sum())
-        flat = np.repeat(run_start - excl, run_len) + np.arange(total)      # dp_pos of f = 0 .. total - 1
+        flat = np.repeat(run_start - excl, run_len) + np.arange(total)      # sh_pos of f = 0 .. total - 1
         if atoms_first_step_only:
             flat = flat[:WAVE]
         steps.append(flat)
