@@ -39,7 +39,8 @@ extern "C" {
  * rsasa_precompute_neighbors_batch, RSASA_ERR_BUFFER_TOO_SMALL; rsasa_accessible_points,
  * rsasa_accessible_points_batch; rsasa_contact_points, rsasa_contact_points_batch; rsasa_group_contacts,
  * rsasa_group_contacts_batch; rsasa_exposure_vectors, rsasa_exposure_vectors_batch, rsasa_sas_volume;
- * rsasa_atom_depth, rsasa_atom_depth_batch. */
+ * rsasa_atom_depth, rsasa_atom_depth_batch; rsasa_surface_components, rsasa_surface_components_batch;
+ * rsasa_half_sphere_exposure, rsasa_half_sphere_exposure_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -669,6 +670,78 @@ int rsasa_surface_components_batch(rsasa_context_t *ctx,
                                    uint64_t *out_dot_offsets,
                                    uint32_t *out_labels, size_t labels_capacity,
                                    uint32_t *out_free, float *out_atom_sasa);
+
+/* ---- half-sphere exposure ----------------------------------------------- */
+
+/* HOW CROWDED the two sides of an atom are: per centre atom the number of
+ * partner atoms of its own structure within a cutoff, split by the plane
+ * through the centre that is normal to a direction the caller gives
+ * (half-sphere exposure, Hamelryck: HSE-up and HSE-down; their sum is the
+ * contact or coordination number).  The cutoff is 12-15 A in practice, four to
+ * five times the reach of the neighbour lists; the cell grid is swept as far
+ * as the cutoff needs.
+ *
+ * Definition.  For a structure, each atom i has centre c_i, a direction u_i
+ * (3 float32 values of any length, zero allowed) and a flag byte f_i: bit 0
+ * (RSASA_HSE_PARTNER) - the atom is a partner, it is counted; bit 1
+ * (RSASA_HSE_CENTRE) - the atom is a centre, it gets a result; the other bits
+ * are ignored.  C is the cutoff.  All arithmetic is float32, unfused, left to
+ * right, as in rsasa_atom_depth:
+ *
+ *     c2   = C * C
+ *     dx   = c_j.x - c_i.x                 (dy, dz alike)
+ *     d2   = dx * dx + dy * dy + dz * dz
+ *     side = dx * u_i.x + dy * u_i.y + dz * u_i.z
+ *     j counts for i  iff  j != i, j in the SAME structure, (f_j & 1), d2 <= c2
+ *     out_up[i]   = number of counting j with side >= 0
+ *     out_down[i] = number of counting j with !(side >= 0)
+ *
+ * An atom without bit 1 gets out_up = out_down = 0.  flags == NULL: every atom
+ * is both a centre and a partner.  dirs == NULL: side is taken as +0 for
+ * everybody, so out_down is all zero and out_up is the contact number.  A NaN
+ * coordinate makes d2 NaN: that atom counts for nobody and, as a centre, gets
+ * 0 / 0.  A NaN component of u_i sends every partner of i to out_down.  A
+ * coincident atom (d2 == 0, side == 0) counts as up.  c2 may overflow to +inf:
+ * then every atom whose d2 is not NaN counts.  Atom ids play no part.  The
+ * counts are integers and have no order, so they can be checked for equality.
+ *
+ * radius and probe_radius are taken, and checked by the rules of the other
+ * calls (probe_radius + largest radius a positive finite number), only because
+ * they fix the cell size of the grid; the result does not depend on them.
+ *
+ * cutoff must be finite and >= 0 (-0.0 is 0); NaN, a negative or an infinite
+ * cutoff returns RSASA_ERR_INVALID_ARGUMENT, and so do NULL columns,
+ * structure_offsets that are not non-decreasing from 0, and out_up or out_down
+ * NULL where there are atoms.  An infinite coordinate returns
+ * RSASA_ERR_GRID_TOO_LARGE and the context stays usable.  No atoms: RSASA_OK.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  No
+ * neighbour lists are built; 8 bytes per atom come back. */
+#define RSASA_HSE_PARTNER 1
+#define RSASA_HSE_CENTRE 2
+
+/* One structure: n_atoms atoms, id nullable (it plays no part).  dirs: [3 * n_atoms]
+ * (x, y, z per atom) or NULL; flags: [n_atoms] or NULL; out_up, out_down:
+ * [n_atoms]. */
+int rsasa_half_sphere_exposure(rsasa_context_t *ctx,
+                               const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, size_t n_atoms,
+                               float probe_radius,
+                               const float *dirs, const uint8_t *flags, float cutoff,
+                               uint32_t *out_up, uint32_t *out_down);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid each; an empty structure is legal);
+ * atoms of other structures never count.  dirs, flags, out_up, out_down run
+ * over structure_offsets[n_structures] atoms. */
+int rsasa_half_sphere_exposure_batch(rsasa_context_t *ctx,
+                                     const float *x, const float *y, const float *z, const float *radius,
+                                     const uint64_t *id,
+                                     const uint32_t *structure_offsets, size_t n_structures,
+                                     float probe_radius,
+                                     const float *dirs, const uint8_t *flags, float cutoff,
+                                     uint32_t *out_up, uint32_t *out_down);
 
 /* ---- contact counts ----------------------------------------------------- */
 

@@ -121,6 +121,10 @@ SYMBOLS = {
                                            _vp, _vp, C.c_size_t, _vp, _vp]),
     "rsasa_surface_components_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,
                                                  C.c_size_t, C.c_float, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_half_sphere_exposure": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp, C.c_float,
+                                             _vp, _vp]),
+    "rsasa_half_sphere_exposure_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp,
+                                                   C.c_float, _vp, _vp]),
     "rsasa_contact_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsasa_contact_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,

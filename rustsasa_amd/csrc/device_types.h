@@ -247,6 +247,18 @@ struct CcArgs {
     float link, link2;                  // two dots are linked when d2 <= link2 = link * link (one float32 product)
 };
 
+// ---- half-sphere exposure (hse.hip, rsasa_half_sphere_exposure*) ----
+// A binned batch (no neighbour lists) with a direction and a flag byte per atom: per centre the partners of its own
+// structure within the cutoff, split by the side of the plane through the centre that is normal to its direction.
+struct HsArgs {
+    BatchView b;                        // the binned batch: grids, cell starts, sorted order
+    const float *dirs;                  // [n_atoms][3], input order, or null: every partner counts as `up`
+    const uint8_t *flags;               // [n_atoms], input order, or null: every atom is centre and partner
+    uint8_t *sorted_flags;              // [n_atoms] the flags in cell-sorted order (k_sort_flags; all 3 where flags is null)
+    float cutoff;                       // a partner counts when d2 <= cutoff * cutoff (one float32 product)
+    uint32_t *up, *down;                // [n_atoms], input order (the definition: include/rustsasa_amd.h)
+};
+
 // ---- contact counts (points.hip, rsasa_contact_points*) ----
 // The same lists and lattice (p.masks unused), per-entry counts out, aligned with NbArgs::out.
 struct CtArgs {
@@ -340,6 +352,8 @@ void launch_mask_free(const PtArgs &a, uint32_t *free, hipStream_t stream);
 void launch_atom_depth(const DpArgs &d, hipStream_t stream);
 // The component labels of the dots (components.hip) from those masks and counts, with CcArgs::dot_offsets.
 void launch_components(const CcArgs &c, hipStream_t stream);
+// The half-sphere counts (hse.hip) on a binned batch: the flags in cell-sorted order, then up[] and down[].
+void launch_half_sphere(const HsArgs &h, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);
 // The 64-bit exclusive scan of the count pass by itself (neighbors.hip): a.counts -> a.offsets[0 .. n_atoms], totals -> a.info.

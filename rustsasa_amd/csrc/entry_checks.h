@@ -63,4 +63,11 @@ inline const char *check_link(float link)
     return nullptr;
 }
 
+// The cutoff of the half-sphere exposure: finite and not negative (-0.0 is 0).
+inline const char *check_cutoff(float cutoff)
+{
+    if (!(cutoff >= 0.0f) || std::isinf(cutoff)) return "cutoff must be finite and not negative";
+    return nullptr;
+}
+
 }  // namespace rsasa

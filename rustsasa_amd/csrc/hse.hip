@@ -1,0 +1,121 @@
+// Half-sphere exposure kernels (rsasa_half_sphere_exposure*, gfx950 only): for every centre the partners of its own
+// structure within a cutoff several cells long, split by the side of the plane through the centre that is normal to the
+// centre's direction.  They need the cell grid of a binned batch and nothing else: no neighbour lists, no lattice.
+//
+//   k_sort_flags    one thread per cell-sorted position: the atom's flag byte, gathered once through sorted_orig (3 where
+//                   the caller gave no flags).  k_half_sphere then reads a partner's bit at the position it reads the
+//                   partner's coordinates from.  Gathered in the sweep instead, the compile listing shows the byte load
+//                   behind an s_waitcnt vmcnt(0) for the sorted_orig load in every trip of the inner loop - two memory
+//                   latencies in a row where the copy issues its byte load and its coordinate load together -, at the same
+//                   66 VGPRs, and a null `flags` is a branch there.
+//   k_half_sphere   one wave per cell-sorted atom i, over the shell sweep of shell_sweep.h; a wave whose atom is no centre
+//                   writes 0 / 0 and returns.  Lanes go over the atoms of a step's runs, 64 at a time; each lane reads
+//                   sorted_xyzr[q] and the flag byte and evaluates the definition (include/rustsasa_amd.h) -
+//                   dx = c_j.x - c_i.x; d2 = dx*dx + dy*dy + dz*dz; side = dx*u.x + dy*u.y + dz*u.z, float32, unfused, left
+//                   to right; j counts iff q != p, bit 0, d2 <= c2 - and the wave adds the popcounts of the ballots of
+//                   (counts, side >= 0) and (counts, !(side >= 0)).  Nothing but the sweep's run tables is in LDS: an atom is
+//                   read by one lane, once, and used for ten operations, so a staged copy would be written and read back
+//                   for nothing (k_atom_depth stages because every staged atom meets every point of the lattice).
+//
+// The reach.  In a structure that passes sh_margins_hold an atom j not seen after shell s >= 1 has, along some axis,
+// D = |x_j - x_i| > (s - 1/8) h in exact arithmetic, h = StructGrid::cell_size (shell_sweep.h, "What an unseen atom
+// implies").  Its float32 d2 is no smaller than the float32 square of that axis' difference: the terms are not negative,
+// and a rounded sum of a float a and a number b >= 0 is at least a (rounding is monotone, a is a float), which holds for
+// both additions wherever the axis' term stands.  The difference carries one rounding and its square one more, so
+//     d2 >= D^2 (1 - 2^-24)^3 > ((s - 1/8) h)^2 (1 - 2^-24)^3
+// as long as the square does not underflow.  The sweep stops after shell s >= 1 when
+//     c2 <= lim2,  lim = (float(s) - 0.5f) * h,  lim2 = lim * lim,  and lim2 >= 1e-30
+// (float(s) - 0.5f is exact, s < 2^18 under the margins; two roundings): lim2 <= ((s - 1/2) h)^2 (1 + 2^-24)^3, and
+// ((s - 1/8) / (s - 1/2))^2 > 1 + 3 / (4 s) > 1 + 2^-19, far above the six roundings' 1 + 2^-21, so every unseen d2 is
+// strictly above lim2 >= c2: no unseen atom counts, and one with d2 == c2 has been seen.  lim2 >= 1e-30 keeps D^2 in the
+// normal range, where the roundings are relative.  (NaN d2 count for nobody, seen or not; c2 = +inf never meets the rule.)
+// Without the margins, or when the rule is never met, the sweep ends when the shells cover the grid (ShCell::s_last),
+// which is always exact.  For cutoff 13 and h = 3.3 the rule is met after shell 5.
+// Compiled with -ffp-contract=off: d2 and side are not fused (the definition is the model's plain float32 arithmetic).
+#include "shell_sweep.h"
+
+namespace rsasa {
+namespace {
+
+__global__ __launch_bounds__(256) void k_sort_flags(HsArgs a)
+{
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.b.n_atoms) return;
+    a.sorted_flags[p] = a.flags ? a.flags[a.b.sorted_orig[p]] : (uint8_t)3u;
+}
+
+__global__ __launch_bounds__(256) void k_half_sphere(HsArgs a)
+{
+    const BatchView &b = a.b;
+    __shared__ uint32_t s_excl[4][kShRuns], s_start[4][kShRuns];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t p = blockIdx.x * 4u + w;
+    if (p >= b.n_atoms) return;
+    const uint32_t orig = b.sorted_orig[p];
+    if ((a.sorted_flags[p] & 2u) == 0u) {  // no centre (the same in every lane)
+        if (lane == 0) {
+            a.up[orig] = 0u;
+            a.down[orig] = 0u;
+        }
+        return;
+    }
+    const StructGrid g = b.grids[b.sid_sorted[p]];
+    const float4 me = b.sorted_xyzr[p];
+    const ShCell cell = sh_cell(g, me);
+    const bool margins = sh_margins_hold(g, b.probe);
+    const bool has_dirs = a.dirs != nullptr;
+    float ux = 0.0f, uy = 0.0f, uz = 0.0f;
+    if (has_dirs) {
+        ux = a.dirs[3u * (size_t)orig];
+        uy = a.dirs[3u * (size_t)orig + 1u];
+        uz = a.dirs[3u * (size_t)orig + 2u];
+    }
+    const float c2 = a.cutoff * a.cutoff;
+
+    uint32_t up = 0, down = 0;
+    for (uint32_t s = 0;; s++) {
+        const ShShell shell = sh_shell(g, cell, s);
+        for (unsigned long long r0 = 0; r0 < shell.n_rows; r0 += kWave) {
+            const uint32_t total = sh_step_runs(b, g, cell, shell, s, r0, s_excl[w], s_start[w]);
+            for (uint32_t f0 = 0; f0 < total; f0 += kWave) {
+                const uint32_t f = f0 + lane;
+                bool counts = false, above = false;
+                if (f < total) {
+                    const uint32_t q = sh_pos(s_excl[w], s_start[w], f);
+                    const float4 o = b.sorted_xyzr[q];
+                    const uint32_t fl = a.sorted_flags[q];
+                    const float dx = o.x - me.x, dy = o.y - me.y, dz = o.z - me.z;
+                    const float d2 = dx * dx + dy * dy + dz * dz;
+                    const float side = has_dirs ? dx * ux + dy * uy + dz * uz : 0.0f;
+                    counts = q != p && (fl & 1u) != 0u && d2 <= c2;
+                    above = side >= 0.0f;
+                }
+                up += (uint32_t)__popcll(ballot64(counts && above));
+                down += (uint32_t)__popcll(ballot64(counts && !above));
+            }
+        }
+        if (s >= cell.s_last) break;  // the shells cover the grid
+        if (margins && s >= 1u) {
+            const float lim = ((float)s - 0.5f) * g.cell_size;
+            const float lim2 = lim * lim;
+            if (c2 <= lim2 && lim2 >= 1e-30f) break;
+        }
+    }
+    if (lane == 0) {
+        a.up[orig] = up;
+        a.down[orig] = down;
+    }
+}
+
+}  // namespace
+
+// sorted_flags[], then up[] and down[] of every atom, on the grid of a binned batch
+void launch_half_sphere(const HsArgs &h, hipStream_t stream)
+{
+    const uint32_t n = h.b.n_atoms;
+    if (!n) return;
+    hipLaunchKernelGGL(k_sort_flags, dim3(cdiv(n, 256)), dim3(256), 0, stream, h);
+    hipLaunchKernelGGL(k_half_sphere, dim3(cdiv(n, 4)), dim3(256), 0, stream, h);
+}
+
+}  // namespace rsasa

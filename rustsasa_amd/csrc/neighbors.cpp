@@ -1,10 +1,11 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h) and of the
 // point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts and
-// group contacts.  The batch's grid is built by the SASA path's kernels in a workspace of the context's own
-// (rsasa_context::nb_ws), then neighbors.hip counts, scans and fills the lists (nb_count, nb_fill).  A point run keeps
-// the lists on the device: every family shares one prologue (pt_count, pt_prepare: lists with the SASA path's cutoff,
-// lattice, PtArgs) and adds its own kernels of points.hip, depth.hip or components.hip and its own downloads.  Every
-// entry point is: resolve_ctx, the argument rules of entry_checks.h, a Cols, the family's run function.
+// group contacts; and of the half-sphere exposure, which needs the grid alone.  The batch's grid is built by the SASA
+// path's kernels in a workspace of the context's own (rsasa_context::nb_ws; nb_grid), then neighbors.hip counts, scans and
+// fills the lists (nb_count, nb_fill).  A point run keeps the lists on the device: every family shares one prologue
+// (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and adds its own kernels of points.hip,
+// depth.hip or components.hip and its own downloads.  Every entry point is: resolve_ctx, the argument rules of
+// entry_checks.h, a Cols, the family's run function.
 // rsasa_sas_volume is plain host arithmetic on what the exposure vectors return.  Host code only.
 #include "engine_internal.h"
 #include "entry_checks.h"
@@ -27,12 +28,10 @@ struct NbHost {  // the pinned block the device's verdicts come back in
     uint64_t last_offset;  // offsets[N], when the caller wants no host copy of the offsets
 };
 
-// The upload, the grid and the counts of a run over columns already in host memory: c.N >= 1 atoms.
-// idx_map (host, nullable): input atom -> the index written to the entries.  out_offsets (nullable): [N + 1], the
-// offsets are copied there.  On RSASA_OK `a` describes the device lists (everything but their entries) and `info` their
-// sizes.  The caller holds the context's mutex and has made its device current.
-int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float probe, float max_r, uint64_t *out_offsets,
-             NbArgs &a, NbInfo &info)
+// The upload and the grid of a run over columns already in host memory: c.N >= 1 atoms.  idx_map (host, nullable) is
+// uploaded beside the columns (RunScratch::map).  On RSASA_OK `v` describes the binned batch.  The caller holds the
+// context's mutex and has made its device current.
+int nb_grid(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float probe, float max_r, BatchView &v)
 {
     int rc;
     rsasa_context::Workspace &W = ctx->nb_ws;
@@ -60,7 +59,6 @@ int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float p
     if (idx_map) RS_HIP(ctx, hipMemcpyAsync(R.map.p, idx_map, N * 4, hipMemcpyHostToDevice, st));
 
     // ---- the grid (without the id check: every id takes part), grown until the cells fit
-    BatchView v{};
     for (int attempt = 0;; attempt++) {
         if ((rc = W.reserve_grid(ctx, N, c.S, segs.size(), ctx->nb_cell_capacity, has_tail, has_id))) return rc;
         if (!segs.empty())
@@ -82,10 +80,22 @@ int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float p
         if ((rc = grid_verdict(ctx, h->status, attempt, ctx->nb_cell_capacity)) == RSASA_OK) break;
         if (rc != kGridAgain) return rc;
     }
+    return RSASA_OK;
+}
 
-    // ---- counts, offsets
+// nb_grid, and the counts of the lists on that grid.  idx_map: input atom -> the index written to the entries.
+// out_offsets (nullable): [N + 1], the offsets are copied there.  On RSASA_OK `a` describes the device lists (everything
+// but their entries) and `info` their sizes.
+int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float probe, float max_r, uint64_t *out_offsets,
+             NbArgs &a, NbInfo &info)
+{
+    int rc;
+    rsasa_context::RunScratch &R = ctx->run;
+    hipStream_t st = ctx->stream;
+    const size_t N = c.N;
     a = NbArgs{};
-    a.b = v;
+    if ((rc = nb_grid(ctx, c, idx_map, probe, max_r, a.b))) return rc;
+    NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
     if ((rc = reserve(ctx, R.counts, N * 4)) || (rc = reserve(ctx, R.offsets, (N + 1) * 8)) ||
         (rc = reserve(ctx, R.parts, 4 * 1024 * 8)) || (rc = reserve(ctx, R.info, sizeof(NbInfo))))
         return rc;
@@ -471,6 +481,41 @@ int gp_run(rsasa_context *ctx, const Cols &c, const uint32_t *group, float probe
     return RSASA_OK;
 }
 
+// ---- half-sphere exposure (rsasa_half_sphere_exposure*) ----
+
+// One run of the half-sphere counts: the grid alone (nb_grid: no counting pass, no lists), the directions and flags
+// beside it, k_sort_flags and k_half_sphere; 8 bytes per atom come back.
+int hs_run(rsasa_context *ctx, const Cols &c, float probe, const float *dirs, const uint8_t *flags, float cutoff,
+           uint32_t *out_up, uint32_t *out_down)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    if (c.N == 0) return RSASA_OK;
+    int rc;
+    rsasa_context::RunScratch &R = ctx->run;
+    hipStream_t st = ctx->stream;
+    const size_t N = c.N;
+    HsArgs h{};
+    if ((rc = nb_grid(ctx, c, nullptr, probe, __builtin_nanf(""), h.b)) || (dirs && (rc = reserve(ctx, R.dirs, N * 12))) ||
+        (flags && (rc = reserve(ctx, R.flags, N))) || (rc = reserve(ctx, R.sorted_flags, N)) ||
+        (rc = reserve(ctx, R.up, N * 4)) || (rc = reserve(ctx, R.down, N * 4)))
+        return rc;
+    if (dirs) RS_HIP(ctx, hipMemcpyAsync(R.dirs.p, dirs, N * 12, hipMemcpyHostToDevice, st));
+    if (flags) RS_HIP(ctx, hipMemcpyAsync(R.flags.p, flags, N, hipMemcpyHostToDevice, st));
+    h.dirs = dirs ? (const float *)R.dirs.p : nullptr;
+    h.flags = flags ? (const uint8_t *)R.flags.p : nullptr;
+    h.sorted_flags = (uint8_t *)R.sorted_flags.p;
+    h.cutoff = cutoff;
+    h.up = (uint32_t *)R.up.p;
+    h.down = (uint32_t *)R.down.p;
+    launch_half_sphere(h, st);
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, download(out_up, h.up, N * 4, st));
+    RS_HIP(ctx, download(out_down, h.down, N * 4, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -613,6 +658,32 @@ int rsasa_surface_components_batch(rsasa_context_t *ctx, const float *x, const f
     RS_ARGS(ctx, check_link(link));
     return cc_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, n_points, link,
                   out_dot_offsets, out_labels, labels_capacity, out_free, out_atom_sasa);
+}
+
+int rsasa_half_sphere_exposure(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, size_t n_atoms, float probe_radius, const float *dirs, const uint8_t *flags,
+                               float cutoff, uint32_t *out_up, uint32_t *out_down)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    RS_ARGS(ctx, check_columns(n_atoms, x, y, z, radius, !n_atoms || (out_up && out_down)));
+    RS_ARGS(ctx, check_cutoff(cutoff));
+    return hs_run(ctx, Cols(x, y, z, radius, id, n_atoms), probe_radius, dirs, flags, cutoff, out_up, out_down);
+}
+
+int rsasa_half_sphere_exposure_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                                     const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures,
+                                     float probe_radius, const float *dirs, const uint8_t *flags, float cutoff,
+                                     uint32_t *out_up, uint32_t *out_down)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    size_t N;
+    RS_ARGS(ctx, check_offsets(structure_offsets, n_structures, N));
+    RS_ARGS(ctx, check_columns(N, x, y, z, radius, !N || (out_up && out_down)));
+    RS_ARGS(ctx, check_cutoff(cutoff));
+    return hs_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, dirs, flags, cutoff,
+                  out_up, out_down);
 }
 
 // No context, no device: double arithmetic in atom order on the host.

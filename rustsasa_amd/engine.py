@@ -376,6 +376,41 @@ class Context:
         the whole batch's radii."""
         return self._surface_components(x, y, z, radius, ids, probe_radius, n_points, link, structure_offsets)
 
+    # ---- half-sphere exposure (how many partners lie on either side of an atom, within a cutoff of several cells) ----
+    def _half_sphere_exposure(self, x, y, z, radius, ids, probe_radius, dirs, flags, cutoff, structure_offsets=_SINGLE):
+        (x, *_), entry = self._entry("half_sphere_exposure", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        if dirs is not None:
+            dirs = _f32(dirs)
+            if dirs.shape != (n, 3):
+                raise ValueError(f"dirs must be an array of shape ({n}, 3) (one direction per atom)")
+        if flags is not None:
+            f = np.asarray(flags)
+            if f.dtype.kind not in "ui" or f.shape != (n,):
+                raise ValueError(f"flags must be a 1-D array of {n} integer entries (uint8, one per atom)")
+            if f.dtype != np.uint8 and f.size and (int(f.min()) < 0 or int(f.max()) > 0xFF):
+                raise ValueError("flags must lie in [0, 256)")
+            flags = np.ascontiguousarray(f, dtype=np.uint8)
+        up, down = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._check(entry(probe_radius, ptr(dirs), ptr(flags), cutoff, ptr(up), ptr(down)))
+        return up, down
+
+    def half_sphere_exposure(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, dirs=None, flags=None,
+                             cutoff: float = 13.0):
+        """rsasa_half_sphere_exposure: (up uint32[N], down uint32[N]).  For every atom i with HSE_CENTRE in flags[i], the
+        atoms j != i with HSE_PARTNER in flags[j] whose float32 d2 to i is at most cutoff * cutoff, evaluated as the
+        header defines it (plain float32, so the counts can be checked for equality): up[i] counts those with
+        (c_j - c_i) . dirs[i] >= 0, down[i] the others; atoms that are no centre get 0 / 0.  flags None: every atom is
+        centre and partner; dirs None: down is zero and up is the contact number.  radius and probe_radius only fix
+        the grid's cell size.  pseudo_cb_directions() gives the HSE-alpha directions of a CA trace."""
+        return self._half_sphere_exposure(x, y, z, radius, ids, probe_radius, dirs, flags, cutoff)
+
+    def half_sphere_exposure_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, dirs=None,
+                                   flags=None, cutoff: float = 13.0):
+        """rsasa_half_sphere_exposure_batch: half_sphere_exposure of every structure (one grid each, atoms of other
+        structures never count), rows in batch order."""
+        return self._half_sphere_exposure(x, y, z, radius, ids, probe_radius, dirs, flags, cutoff, structure_offsets)
+
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
     def _contact_points(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -598,6 +633,36 @@ def residue_depth(depth, residue_offsets):
                 total += float(v)
             out[r] = total / (e - b)
     return out
+
+
+HSE_PARTNER = 1  # flag bits of half_sphere_exposure: the atom is counted / the atom gets a result
+HSE_CENTRE = 2
+
+
+def pseudo_cb_directions(ca_xyz, chain_offsets) -> np.ndarray:
+    """The HSE-alpha directions of a CA trace, float32[N, 3]: for every CA that has both chain neighbours, the sum of
+    the unit vectors from CA(i - 1) and from CA(i + 1) towards CA(i) (it points roughly where the side chain does).
+    ca_xyz is [N, 3]; chain c is rows [chain_offsets[c], chain_offsets[c + 1]).  Chain ends (and chains of fewer than
+    three atoms) get a zero vector, and so does the share of a neighbour that coincides with the atom.  Host
+    arithmetic in float64, rounded once at the end."""
+    ca = np.asarray(ca_xyz, dtype=np.float64)
+    off = np.asarray(chain_offsets, dtype=np.int64)
+    if ca.ndim != 2 or ca.shape[1] != 3:
+        raise ValueError("ca_xyz must be an array of shape (N, 3)")
+    if off.ndim != 1 or off.shape[0] < 1 or off[0] != 0 or off[-1] != ca.shape[0] or np.any(np.diff(off) < 0):
+        raise ValueError("chain_offsets must be non-decreasing from 0 to N")
+    n = ca.shape[0]
+    out = np.zeros((n, 3), np.float64)
+    interior = np.ones(n, bool)
+    interior[off[:-1][off[:-1] < n]] = False  # (an empty chain's offset is its successor's first atom, or N)
+    interior[off[1:][off[1:] > 0] - 1] = False
+    i = np.flatnonzero(interior)
+    for nb in (i - 1, i + 1):
+        d = ca[i] - ca[nb]
+        length = np.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2])
+        ok = length > 0.0
+        out[i[ok]] += d[ok] / length[ok, None]
+    return out.astype(np.float32)
 
 
 def default_link(radius, probe_radius: float = 1.4, n_points: int = 100) -> np.float32:
