@@ -40,7 +40,8 @@ extern "C" {
  * rsasa_accessible_points_batch; rsasa_contact_points, rsasa_contact_points_batch; rsasa_group_contacts,
  * rsasa_group_contacts_batch; rsasa_exposure_vectors, rsasa_exposure_vectors_batch, rsasa_sas_volume;
  * rsasa_atom_depth, rsasa_atom_depth_batch; rsasa_surface_components, rsasa_surface_components_batch;
- * rsasa_half_sphere_exposure, rsasa_half_sphere_exposure_batch. */
+ * rsasa_half_sphere_exposure, rsasa_half_sphere_exposure_batch; rsasa_within_t, rsasa_atoms_within,
+ * rsasa_atoms_within_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -54,7 +55,8 @@ typedef enum rsasa_status {
     RSASA_ERR_QUEUE_FULL = -7,       /* rsasa_host_batch_enqueue: eight batches are queued and not yet waited for */
     RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*: out_entries is NULL or holds
                                         fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
-                                        the same for its row buffers */
+                                        the same for its row buffers; rsasa_surface_components*: for out_labels;
+                                        rsasa_atoms_within*: for its out_entries */
 } rsasa_status;
 
 /* Mirrors `Atom` (reference src/structures/atomic.rs:13-24) without the
@@ -742,6 +744,107 @@ int rsasa_half_sphere_exposure_batch(rsasa_context_t *ctx,
                                      float probe_radius,
                                      const float *dirs, const uint8_t *flags, float cutoff,
                                      uint32_t *out_up, uint32_t *out_down);
+
+/* ---- atoms within a cutoff ---------------------------------------------- */
+
+/* WHO is within a cutoff of an atom: per centre atom the list of the partner
+ * atoms of its own structure within a cutoff, each with its squared distance -
+ * what rsasa_half_sphere_exposure counts, named.  Residue contact maps (closest
+ * heavy atoms within 4.5 / 6 / 8 A), CA or CB contact maps at 8-10 A, contact
+ * order, residue-interaction networks and the radius graphs of structure
+ * networks start from these lists; the neighbour lists of
+ * rsasa_precompute_neighbors stop at r_i + max_r + 2 probe (about 6.5 A).
+ *
+ * Definition.  For a structure, each atom i has centre c_i and a flag byte f_i:
+ * bit 0 (RSASA_WITHIN_PARTNER) - the atom is a partner, it is listed; bit 1
+ * (RSASA_WITHIN_CENTRE) - the atom is a centre, it gets a list; the other bits
+ * are ignored (the bits of RSASA_HSE_PARTNER / RSASA_HSE_CENTRE).  C is the
+ * cutoff.  All arithmetic is float32, unfused, left to right, exactly as in
+ * rsasa_half_sphere_exposure:
+ *
+ *     c2 = C * C
+ *     dx = c_j.x - c_i.x                 (dy, dz alike)
+ *     d2 = dx * dx + dy * dy + dz * dz
+ *     j is in i's list  iff  (f_i & 2), j != i, j in the SAME structure,
+ *                            (f_j & 1), d2 <= c2,
+ *                            and, when upper_only != 0, j > i
+ *
+ * Lists.  The list of atom i is out_entries[out_offsets[i] .. out_offsets[i+1]).
+ * An atom without bit 1 has an empty list.  flags == NULL: every atom is both
+ * a centre and a partner.  Each entry holds the float32 d2 of the definition
+ * and idx, the partner's index within its structure (in the one-structure
+ * call: its input index).
+ *
+ * Order.  Every list is ascending by (d2, idx) - the order of the 64-bit key
+ * (bits(d2) << 32) | idx: d2 in a list is never NaN or negative, so its bits
+ * order like the numbers; +inf can appear only when c2 overflows, and orders
+ * last.  The result can therefore be compared byte for byte.
+ *
+ * Symmetry.  d2 is the same bit pattern in both directions (float subtraction
+ * is exactly antisymmetric): with every flag 3 and upper_only == 0, j is in
+ * i's list with d2 exactly when i is in j's with the same d2.
+ *
+ * Relation to the half-sphere exposure.  With upper_only == 0,
+ * out_offsets[i+1] - out_offsets[i] equals out_up[i] + out_down[i] of
+ * rsasa_half_sphere_exposure for the same flags and cutoff.
+ *
+ * A NaN coordinate makes d2 NaN: that atom is in nobody's list and, as a
+ * centre, has an empty list.  c2 may overflow to +inf: then every partner whose
+ * d2 is not NaN is listed.  Atom ids play no part.
+ *
+ * radius and probe_radius are taken, and checked by the rules of the other
+ * calls (probe_radius + largest radius a positive finite number), only because
+ * they fix the cell size of the grid; the result does not depend on them.
+ *
+ * cutoff must be finite and >= 0 (-0.0 is 0); NaN, a negative or an infinite
+ * cutoff returns RSASA_ERR_INVALID_ARGUMENT, and so do NULL columns,
+ * structure_offsets that are not non-decreasing from 0, and out_offsets NULL.
+ * An infinite coordinate returns RSASA_ERR_GRID_TOO_LARGE and the context stays
+ * usable.  No atoms: RSASA_OK with out_offsets[0] = 0.
+ *
+ * Sizing, as in rsasa_precompute_neighbors: out_offsets is always written (on
+ * success and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_entries is NULL or
+ * entries_capacity < out_offsets[n], nothing else is written and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned: call once to size, allocate, call
+ * again - or pass a generous buffer (all-atom lists of proteins hold about
+ * 0.2 C^3 entries each, C in A).  The entries take 8 bytes each on the device
+ * as well; a failed reservation returns RSASA_ERR_OUT_OF_MEMORY and the context
+ * stays usable.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  No
+ * neighbour lists are built. */
+typedef struct rsasa_within {
+    float d2;     /* squared distance to the centre, float32 as defined above */
+    uint32_t idx; /* the partner's index within its structure */
+} rsasa_within_t; /* 8 bytes */
+#define RSASA_WITHIN_PARTNER 1
+#define RSASA_WITHIN_CENTRE 2
+
+/* One structure: n_atoms atoms, id nullable (it plays no part).  flags:
+ * [n_atoms] or NULL; out_offsets: [n_atoms + 1]; out_entries:
+ * [entries_capacity]. */
+int rsasa_atoms_within(rsasa_context_t *ctx,
+                       const float *x, const float *y, const float *z, const float *radius,
+                       const uint64_t *id, size_t n_atoms,
+                       float probe_radius,
+                       const uint8_t *flags, float cutoff, int upper_only,
+                       uint64_t *out_offsets,
+                       rsasa_within_t *out_entries, size_t entries_capacity);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid each; an empty structure is legal); no
+ * list crosses structures.  flags runs over structure_offsets[n_structures]
+ * atoms; out_offsets is batch-global [structure_offsets[n_structures] + 1]; idx
+ * is the index within the partner's (= the centre's) structure. */
+int rsasa_atoms_within_batch(rsasa_context_t *ctx,
+                             const float *x, const float *y, const float *z, const float *radius,
+                             const uint64_t *id,
+                             const uint32_t *structure_offsets, size_t n_structures,
+                             float probe_radius,
+                             const uint8_t *flags, float cutoff, int upper_only,
+                             uint64_t *out_offsets,
+                             rsasa_within_t *out_entries, size_t entries_capacity);
 
 /* ---- contact counts ----------------------------------------------------- */
 

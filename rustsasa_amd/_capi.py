@@ -33,6 +33,12 @@ assert ATOM_DTYPE.itemsize == 24
 NEIGHBOR_DTYPE = np.dtype([("threshold_squared", "<f4"), ("idx", "<u4")])
 assert NEIGHBOR_DTYPE.itemsize == 8
 
+# numpy image of rsasa_within_t, and the flag bits of rsasa_atoms_within* (those of the half-sphere exposure)
+WITHIN_DTYPE = np.dtype([("d2", "<f4"), ("idx", "<u4")])
+assert WITHIN_DTYPE.itemsize == 8
+WITHIN_PARTNER = 1
+WITHIN_CENTRE = 2
+
 
 class RsasaError(RuntimeError):
     def __init__(self, status: int, message: str):
@@ -125,6 +131,10 @@ SYMBOLS = {
                                              _vp, _vp]),
     "rsasa_half_sphere_exposure_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp,
                                                    C.c_float, _vp, _vp]),
+    "rsasa_atoms_within": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_float, C.c_int,
+                                     _vp, _vp, C.c_size_t]),
+    "rsasa_atoms_within_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_float,
+                                           C.c_int, _vp, _vp, C.c_size_t]),
     "rsasa_contact_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsasa_contact_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,

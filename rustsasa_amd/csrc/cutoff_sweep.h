@@ -1,0 +1,38 @@
+// The stop rule of a shell sweep (shell_sweep.h) that accepts an atom by d2 <= c2: shared by k_half_sphere (hse.hip) and by
+// k_within_count / k_within_fill (within.hip), which all evaluate, for the wave's atom i at c_i and an atom j at c_j,
+//     dx = c_j.x - c_i.x (dy, dz alike);  d2 = dx*dx + dy*dy + dz*dz      float32, unfused, left to right
+// and take j only if d2 <= c2 (whatever else they ask of j only removes atoms).  Device only, gfx950 only.
+//
+// The reach.  In a structure that passes sh_margins_hold an atom j not seen after shell s >= 1 has, along some axis,
+// D = |x_j - x_i| > (s - 1/8) h in exact arithmetic, h = StructGrid::cell_size (shell_sweep.h, "What an unseen atom
+// implies").  Its float32 d2 is no smaller than the float32 square of that axis' difference: the terms are not negative,
+// and a rounded sum of a float a and a number b >= 0 is at least a (rounding is monotone, a is a float), which holds for
+// both additions wherever the axis' term stands.  The difference carries one rounding and its square one more, so
+//     d2 >= D^2 (1 - 2^-24)^3 > ((s - 1/8) h)^2 (1 - 2^-24)^3
+// as long as the square does not underflow.  The sweep stops after shell s >= 1 when
+//     c2 <= lim2,  lim = (float(s) - 0.5f) * h,  lim2 = lim * lim,  and lim2 >= 1e-30
+// (float(s) - 0.5f is exact, s < 2^18 under the margins; two roundings): lim2 <= ((s - 1/2) h)^2 (1 + 2^-24)^3, and
+// ((s - 1/8) / (s - 1/2))^2 > 1 + 3 / (4 s) > 1 + 2^-19, far above the six roundings' 1 + 2^-21, so every unseen d2 is
+// strictly above lim2 >= c2: no unseen atom is accepted, and one with d2 == c2 has been seen.  lim2 >= 1e-30 keeps D^2 in
+// the normal range, where the roundings are relative.  (NaN d2 is accepted for nobody, seen or not; c2 = +inf never meets
+// the rule.)  Without the margins, or when the rule is never met, the caller's sweep ends when the shells cover the grid
+// (ShCell::s_last), which is always exact.  For cutoff 13 and h = 3.3 the rule is met after shell 5.
+#pragma once
+#include "shell_sweep.h"
+
+namespace rsasa {
+namespace {
+
+// Whether the sweep may stop after shell s: margins = sh_margins_hold of the structure, h its cell size, c2 = C * C.
+__device__ __forceinline__ bool sh_cutoff_reached(bool margins, uint32_t s, float h, float c2)
+{
+    if (margins && s >= 1u) {
+        const float lim = ((float)s - 0.5f) * h;
+        const float lim2 = lim * lim;
+        if (c2 <= lim2 && lim2 >= 1e-30f) return true;
+    }
+    return false;
+}
+
+}  // namespace
+}  // namespace rsasa

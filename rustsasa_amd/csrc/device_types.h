@@ -200,6 +200,8 @@ struct NbArgs {
     uint2 *out;                      // (threshold_squared bits, idx) = rsasa_neighbor_t
     NbKey *spill;
     NbSpillRec *spill_recs;
+    uint32_t stage;                  // the keys the run's fill kernel stages per list: the scan counts the longer lists into
+                                     // NbInfo::spill_entries / spill_atoms (neighbor_stage_capacity, within_stage_capacity)
 };
 
 // ---- accessible points (points.hip, rsasa_accessible_points*) ----
@@ -257,6 +259,18 @@ struct HsArgs {
     uint8_t *sorted_flags;              // [n_atoms] the flags in cell-sorted order (k_sort_flags; all 3 where flags is null)
     float cutoff;                       // a partner counts when d2 <= cutoff * cutoff (one float32 product)
     uint32_t *up, *down;                // [n_atoms], input order (the definition: include/rustsasa_amd.h)
+};
+
+// ---- atoms within a cutoff (within.hip, rsasa_atoms_within*) ----
+// A binned batch (no neighbour lists) with a flag byte per atom in cell-sorted order: per centre the list of the partners
+// of its own structure within the cutoff, as entries (float bits of d2, idx) sorted by (d2, idx).
+struct WnArgs {
+    NbArgs n;                           // the binned batch; counts, offsets, parts, info as in a neighbour run (idx_map null);
+                                        // out: the entries (d2 bits, idx within the structure) = rsasa_within_t; spill (thr =
+                                        // d2) and spill_recs for the lists longer than the staging, as k_neighbor_fill uses them
+    const uint8_t *sorted_flags;        // [n_atoms] HsArgs::sorted_flags (k_sort_flags)
+    float cutoff;                       // a partner is listed when d2 <= cutoff * cutoff (one float32 product)
+    uint32_t upper_only;                // nonzero: only partners with a larger index than the centre's
 };
 
 // ---- contact counts (points.hip, rsasa_contact_points*) ----
@@ -354,6 +368,17 @@ void launch_atom_depth(const DpArgs &d, hipStream_t stream);
 void launch_components(const CcArgs &c, hipStream_t stream);
 // The half-sphere counts (hse.hip) on a binned batch: the flags in cell-sorted order, then up[] and down[].
 void launch_half_sphere(const HsArgs &h, hipStream_t stream);
+// The keys k_neighbor_fill / k_within_fill stage per list in LDS: what NbArgs::stage is set to for their runs.
+uint32_t neighbor_stage_capacity();
+uint32_t within_stage_capacity();
+// The flags in cell-sorted order alone (hse.hip): h.b, h.flags -> h.sorted_flags.
+void launch_sort_flags(const HsArgs &h, hipStream_t stream);
+// The lists of the atoms within a cutoff (within.hip) on a binned batch with sorted flags: counts, offsets and NbInfo
+// (with NbArgs::stage = within_stage_capacity()); then the entries.
+void launch_within_count(const WnArgs &w, hipStream_t stream);
+void launch_within_fill(const WnArgs &w, uint64_t spill_atoms, hipStream_t stream);
+// The ranking of the long lists by itself (neighbors.hip): a.spill, a.spill_recs -> a.out, one workgroup per list.
+void launch_neighbor_rank_spill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);
 // The 64-bit exclusive scan of the count pass by itself (neighbors.hip): a.counts -> a.offsets[0 .. n_atoms], totals -> a.info.

@@ -17,22 +17,10 @@
 //                   read by one lane, once, and used for ten operations, so a staged copy would be written and read back
 //                   for nothing (k_atom_depth stages because every staged atom meets every point of the lattice).
 //
-// The reach.  In a structure that passes sh_margins_hold an atom j not seen after shell s >= 1 has, along some axis,
-// D = |x_j - x_i| > (s - 1/8) h in exact arithmetic, h = StructGrid::cell_size (shell_sweep.h, "What an unseen atom
-// implies").  Its float32 d2 is no smaller than the float32 square of that axis' difference: the terms are not negative,
-// and a rounded sum of a float a and a number b >= 0 is at least a (rounding is monotone, a is a float), which holds for
-// both additions wherever the axis' term stands.  The difference carries one rounding and its square one more, so
-//     d2 >= D^2 (1 - 2^-24)^3 > ((s - 1/8) h)^2 (1 - 2^-24)^3
-// as long as the square does not underflow.  The sweep stops after shell s >= 1 when
-//     c2 <= lim2,  lim = (float(s) - 0.5f) * h,  lim2 = lim * lim,  and lim2 >= 1e-30
-// (float(s) - 0.5f is exact, s < 2^18 under the margins; two roundings): lim2 <= ((s - 1/2) h)^2 (1 + 2^-24)^3, and
-// ((s - 1/8) / (s - 1/2))^2 > 1 + 3 / (4 s) > 1 + 2^-19, far above the six roundings' 1 + 2^-21, so every unseen d2 is
-// strictly above lim2 >= c2: no unseen atom counts, and one with d2 == c2 has been seen.  lim2 >= 1e-30 keeps D^2 in the
-// normal range, where the roundings are relative.  (NaN d2 count for nobody, seen or not; c2 = +inf never meets the rule.)
-// Without the margins, or when the rule is never met, the sweep ends when the shells cover the grid (ShCell::s_last),
-// which is always exact.  For cutoff 13 and h = 3.3 the rule is met after shell 5.
+// The reach.  The sweep stops after shell s >= 1 once c2 <= ((s - 1/2) h)^2, or when the shells cover the grid: the rule, and
+// the proof that no unseen atom can count, ties included, are in cutoff_sweep.h (within.hip sweeps by the same rule).
 // Compiled with -ffp-contract=off: d2 and side are not fused (the definition is the model's plain float32 arithmetic).
-#include "shell_sweep.h"
+#include "cutoff_sweep.h"
 
 namespace rsasa {
 namespace {
@@ -95,11 +83,7 @@ __global__ __launch_bounds__(256) void k_half_sphere(HsArgs a)
             }
         }
         if (s >= cell.s_last) break;  // the shells cover the grid
-        if (margins && s >= 1u) {
-            const float lim = ((float)s - 0.5f) * g.cell_size;
-            const float lim2 = lim * lim;
-            if (c2 <= lim2 && lim2 >= 1e-30f) break;
-        }
+        if (sh_cutoff_reached(margins, s, g.cell_size, c2)) break;
     }
     if (lane == 0) {
         a.up[orig] = up;
@@ -109,12 +93,20 @@ __global__ __launch_bounds__(256) void k_half_sphere(HsArgs a)
 
 }  // namespace
 
+// sorted_flags[] of every atom (h.b, h.flags, h.sorted_flags: nothing else of `h` is read)
+void launch_sort_flags(const HsArgs &h, hipStream_t stream)
+{
+    const uint32_t n = h.b.n_atoms;
+    if (!n) return;
+    hipLaunchKernelGGL(k_sort_flags, dim3(cdiv(n, 256)), dim3(256), 0, stream, h);
+}
+
 // sorted_flags[], then up[] and down[] of every atom, on the grid of a binned batch
 void launch_half_sphere(const HsArgs &h, hipStream_t stream)
 {
     const uint32_t n = h.b.n_atoms;
     if (!n) return;
-    hipLaunchKernelGGL(k_sort_flags, dim3(cdiv(n, 256)), dim3(256), 0, stream, h);
+    launch_sort_flags(h, stream);
     hipLaunchKernelGGL(k_half_sphere, dim3(cdiv(n, 4)), dim3(256), 0, stream, h);
 }
 

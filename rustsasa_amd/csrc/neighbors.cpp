@@ -1,6 +1,7 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h) and of the
 // point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts and
-// group contacts; and of the half-sphere exposure, which needs the grid alone.  The batch's grid is built by the SASA
+// group contacts; and of the half-sphere exposure and the lists within a cutoff, which need the grid alone.  The batch's
+// grid is built by the SASA
 // path's kernels in a workspace of the context's own (rsasa_context::nb_ws; nb_grid), then neighbors.hip counts, scans and
 // fills the lists (nb_count, nb_fill).  A point run keeps the lists on the device: every family shares one prologue
 // (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and adds its own kernels of points.hip,
@@ -83,19 +84,12 @@ int nb_grid(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float pr
     return RSASA_OK;
 }
 
-// nb_grid, and the counts of the lists on that grid.  idx_map: input atom -> the index written to the entries.
-// out_offsets (nullable): [N + 1], the offsets are copied there.  On RSASA_OK `a` describes the device lists (everything
-// but their entries) and `info` their sizes.
-int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float probe, float max_r, uint64_t *out_offsets,
-             NbArgs &a, NbInfo &info)
+// The buffers a count pass and its scan write (counts, offsets, parts, a cleared NbInfo) for the N atoms of a.b, and
+// the length above which the run's fill kernel takes a list for long.
+int nb_scan_buffers(rsasa_context *ctx, size_t N, uint32_t stage, NbArgs &a)
 {
     int rc;
     rsasa_context::RunScratch &R = ctx->run;
-    hipStream_t st = ctx->stream;
-    const size_t N = c.N;
-    a = NbArgs{};
-    if ((rc = nb_grid(ctx, c, idx_map, probe, max_r, a.b))) return rc;
-    NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
     if ((rc = reserve(ctx, R.counts, N * 4)) || (rc = reserve(ctx, R.offsets, (N + 1) * 8)) ||
         (rc = reserve(ctx, R.parts, 4 * 1024 * 8)) || (rc = reserve(ctx, R.info, sizeof(NbInfo))))
         return rc;
@@ -103,9 +97,17 @@ int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float p
     a.offsets = (unsigned long long *)R.offsets.p;
     a.parts = (unsigned long long *)R.parts.p;
     a.info = (NbInfo *)R.info.p;
-    a.idx_map = idx_map ? (const uint32_t *)R.map.p : nullptr;
-    RS_HIP(ctx, hipMemsetAsync(a.info, 0, sizeof(NbInfo), st));
-    launch_neighbor_count(a, st);
+    a.stage = stage;
+    RS_HIP(ctx, hipMemsetAsync(a.info, 0, sizeof(NbInfo), ctx->stream));
+    return RSASA_OK;
+}
+
+// What a queued count pass and scan found: waits for them; `info` gets the lists' sizes and out_offsets (nullable:
+// [N + 1]) the offsets.
+int nb_sizes(rsasa_context *ctx, const NbArgs &a, size_t N, uint64_t *out_offsets, NbInfo &info)
+{
+    hipStream_t st = ctx->stream;
+    NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
     RS_HIP(ctx, hipMemcpyAsync(&h->info, a.info, sizeof(NbInfo), hipMemcpyDeviceToHost, st));
     if (out_offsets) RS_HIP(ctx, hipMemcpyAsync(out_offsets, a.offsets, (N + 1) * 8, hipMemcpyDeviceToHost, st));
     else RS_HIP(ctx, hipMemcpyAsync(&h->last_offset, a.offsets + N, 8, hipMemcpyDeviceToHost, st));
@@ -113,12 +115,30 @@ int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float p
     RS_HIP(ctx, hipStreamSynchronize(st));
     info = h->info;
     if (info.total != (out_offsets ? out_offsets[N] : h->last_offset))
-        return fail(ctx, RSASA_ERR_INTERNAL, "neighbour offsets disagree with their total");
+        return fail(ctx, RSASA_ERR_INTERNAL, "list offsets disagree with their total");
     return RSASA_OK;
 }
 
-// The entries of the lists nb_count sized (info.total >= 1), sorted, in a.out on the device.
-int nb_fill(rsasa_context *ctx, NbArgs &a, const NbInfo &info)
+// nb_grid, and the counts of the lists on that grid.  idx_map: input atom -> the index written to the entries.
+// out_offsets (nullable): [N + 1], the offsets are copied there.  On RSASA_OK `a` describes the device lists (everything
+// but their entries) and `info` their sizes.
+int nb_count(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float probe, float max_r, uint64_t *out_offsets,
+             NbArgs &a, NbInfo &info)
+{
+    int rc;
+    a = NbArgs{};
+    if ((rc = nb_grid(ctx, c, idx_map, probe, max_r, a.b)) || (rc = nb_scan_buffers(ctx, c.N, neighbor_stage_capacity(), a)))
+        return rc;
+    a.idx_map = idx_map ? (const uint32_t *)ctx->run.map.p : nullptr;
+    launch_neighbor_count(a, ctx->stream);
+    return nb_sizes(ctx, a, c.N, out_offsets, info);
+}
+
+// The entries of the lists a count pass sized (info.total >= 1), sorted, in a.out on the device: reserves them and the
+// long lists' scratch, runs `launch(info.spill_atoms)` - the family's fill kernels over `a` - and checks that the fill
+// pass agreed with the count pass.
+template <class Launch>
+int nb_fill_by(rsasa_context *ctx, NbArgs &a, const NbInfo &info, Launch launch)
 {
     int rc;
     rsasa_context::RunScratch &R = ctx->run;
@@ -131,13 +151,19 @@ int nb_fill(rsasa_context *ctx, NbArgs &a, const NbInfo &info)
     a.out = (uint2 *)R.entries.p;
     a.spill = info.spill_atoms ? (NbKey *)R.spill.p : nullptr;
     a.spill_recs = info.spill_atoms ? (NbSpillRec *)R.recs.p : nullptr;
-    launch_neighbor_fill(a, info.spill_atoms, st);
+    launch(info.spill_atoms);
     RS_HIP(ctx, hipMemcpyAsync(&h->info, a.info, sizeof(NbInfo), hipMemcpyDeviceToHost, st));
     RS_HIP(ctx, hipGetLastError());
     RS_HIP(ctx, hipStreamSynchronize(st));
     if (h->info.mismatch || h->info.spill_cursor != info.spill_entries || h->info.spill_recs != info.spill_atoms)
-        return fail(ctx, RSASA_ERR_INTERNAL, "the neighbour fill pass disagrees with its count pass");
+        return fail(ctx, RSASA_ERR_INTERNAL, "the fill pass of the lists disagrees with its count pass");
     return RSASA_OK;
+}
+
+// The entries of the lists nb_count sized (info.total >= 1).
+int nb_fill(rsasa_context *ctx, NbArgs &a, const NbInfo &info)
+{
+    return nb_fill_by(ctx, a, info, [&](uint64_t spill_atoms) { launch_neighbor_fill(a, spill_atoms, ctx->stream); });
 }
 
 // Queues the copy of `bytes` from the device into a host array that the caller may have left out.
@@ -481,7 +507,20 @@ int gp_run(rsasa_context *ctx, const Cols &c, const uint32_t *group, float probe
     return RSASA_OK;
 }
 
-// ---- half-sphere exposure (rsasa_half_sphere_exposure*) ----
+// ---- half-sphere exposure (rsasa_half_sphere_exposure*) and atoms within a cutoff (rsasa_atoms_within*) ----
+
+// The flag bytes of a run on the grid alone (flags: host, [N], nullable) beside the binned batch h.b: uploaded, with
+// room for their cell-sorted copy; k_sort_flags (launch_half_sphere, launch_sort_flags) then writes h.sorted_flags.
+int hs_flags(rsasa_context *ctx, size_t N, const uint8_t *flags, HsArgs &h)
+{
+    int rc;
+    rsasa_context::RunScratch &R = ctx->run;
+    if ((flags && (rc = reserve(ctx, R.flags, N))) || (rc = reserve(ctx, R.sorted_flags, N))) return rc;
+    if (flags) RS_HIP(ctx, hipMemcpyAsync(R.flags.p, flags, N, hipMemcpyHostToDevice, ctx->stream));
+    h.flags = flags ? (const uint8_t *)R.flags.p : nullptr;
+    h.sorted_flags = (uint8_t *)R.sorted_flags.p;
+    return RSASA_OK;
+}
 
 // One run of the half-sphere counts: the grid alone (nb_grid: no counting pass, no lists), the directions and flags
 // beside it, k_sort_flags and k_half_sphere; 8 bytes per atom come back.
@@ -497,14 +536,10 @@ int hs_run(rsasa_context *ctx, const Cols &c, float probe, const float *dirs, co
     const size_t N = c.N;
     HsArgs h{};
     if ((rc = nb_grid(ctx, c, nullptr, probe, __builtin_nanf(""), h.b)) || (dirs && (rc = reserve(ctx, R.dirs, N * 12))) ||
-        (flags && (rc = reserve(ctx, R.flags, N))) || (rc = reserve(ctx, R.sorted_flags, N)) ||
-        (rc = reserve(ctx, R.up, N * 4)) || (rc = reserve(ctx, R.down, N * 4)))
+        (rc = hs_flags(ctx, N, flags, h)) || (rc = reserve(ctx, R.up, N * 4)) || (rc = reserve(ctx, R.down, N * 4)))
         return rc;
     if (dirs) RS_HIP(ctx, hipMemcpyAsync(R.dirs.p, dirs, N * 12, hipMemcpyHostToDevice, st));
-    if (flags) RS_HIP(ctx, hipMemcpyAsync(R.flags.p, flags, N, hipMemcpyHostToDevice, st));
     h.dirs = dirs ? (const float *)R.dirs.p : nullptr;
-    h.flags = flags ? (const uint8_t *)R.flags.p : nullptr;
-    h.sorted_flags = (uint8_t *)R.sorted_flags.p;
     h.cutoff = cutoff;
     h.up = (uint32_t *)R.up.p;
     h.down = (uint32_t *)R.down.p;
@@ -512,6 +547,40 @@ int hs_run(rsasa_context *ctx, const Cols &c, float probe, const float *dirs, co
     RS_HIP(ctx, hipGetLastError());
     RS_HIP(ctx, download(out_up, h.up, N * 4, st));
     RS_HIP(ctx, download(out_down, h.down, N * 4, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+// One run of the lists within a cutoff: the grid alone and the flags as in hs_run, k_within_count and the neighbour
+// runs' scan, the sizing rule of nb_run, then k_within_fill (and the ranking of the long lists) and 8 bytes per entry back.
+int wn_run(rsasa_context *ctx, const Cols &c, float probe, const uint8_t *flags, float cutoff, int upper_only,
+           uint64_t *out_offsets, rsasa_within_t *out_entries, size_t cap)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    if (c.N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    int rc;
+    hipStream_t st = ctx->stream;
+    HsArgs h{};
+    WnArgs w{};
+    NbInfo info{};
+    if ((rc = nb_grid(ctx, c, nullptr, probe, __builtin_nanf(""), h.b)) || (rc = hs_flags(ctx, c.N, flags, h))) return rc;
+    w.n.b = h.b;
+    if ((rc = nb_scan_buffers(ctx, c.N, within_stage_capacity(), w.n))) return rc;
+    w.sorted_flags = h.sorted_flags;
+    w.cutoff = cutoff;
+    w.upper_only = upper_only ? 1u : 0u;
+    launch_sort_flags(h, st);
+    launch_within_count(w, st);
+    if ((rc = nb_sizes(ctx, w.n, c.N, out_offsets, info))) return rc;
+    if (!out_entries || cap < info.total)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_entries is NULL or holds fewer entries than out_offsets[n]");
+    if (info.total == 0) return RSASA_OK;
+    if ((rc = nb_fill_by(ctx, w.n, info, [&](uint64_t spill_atoms) { launch_within_fill(w, spill_atoms, st); }))) return rc;
+    RS_HIP(ctx, hipMemcpyAsync(out_entries, w.n.out, info.total * 8, hipMemcpyDeviceToHost, st));
     RS_HIP(ctx, hipStreamSynchronize(st));
     return RSASA_OK;
 }
@@ -684,6 +753,33 @@ int rsasa_half_sphere_exposure_batch(rsasa_context_t *ctx, const float *x, const
     RS_ARGS(ctx, check_cutoff(cutoff));
     return hs_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, dirs, flags, cutoff,
                   out_up, out_down);
+}
+
+int rsasa_atoms_within(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                       const uint64_t *id, size_t n_atoms, float probe_radius, const uint8_t *flags, float cutoff,
+                       int upper_only, uint64_t *out_offsets, rsasa_within_t *out_entries, size_t entries_capacity)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    RS_ARGS(ctx, check_columns(n_atoms, x, y, z, radius, out_offsets));
+    RS_ARGS(ctx, check_cutoff(cutoff));
+    return wn_run(ctx, Cols(x, y, z, radius, id, n_atoms), probe_radius, flags, cutoff, upper_only, out_offsets, out_entries,
+                  entries_capacity);
+}
+
+int rsasa_atoms_within_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                             const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                             const uint8_t *flags, float cutoff, int upper_only, uint64_t *out_offsets,
+                             rsasa_within_t *out_entries, size_t entries_capacity)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    size_t N;
+    RS_ARGS(ctx, check_offsets(structure_offsets, n_structures, N));
+    RS_ARGS(ctx, check_columns(N, x, y, z, radius, out_offsets));
+    RS_ARGS(ctx, check_cutoff(cutoff));
+    return wn_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, flags, cutoff,
+                  upper_only, out_offsets, out_entries, entries_capacity);
 }
 
 // No context, no device: double arithmetic in atom order on the host.

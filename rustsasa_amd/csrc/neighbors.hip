@@ -144,7 +144,7 @@ __device__ __forceinline__ void nb_scan_range(uint32_t n, uint32_t &begin, uint3
     end = (uint32_t)min(b0 + chunk, (unsigned long long)n);
 }
 
-// sum, max, and the sum and number of the counts above the staging (parts[4 * block ..])
+// sum, max, and the sum and number of the counts above the run's staging, NbArgs::stage (parts[4 * block ..])
 __global__ __launch_bounds__(256) void k_nb_scan_reduce(NbArgs a)
 {
     __shared__ unsigned long long smem[4][4];
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void k_nb_scan_reduce(NbArgs a)
         const uint32_t c = a.counts[i];
         sum += c;
         mx = max(mx, (unsigned long long)c);
-        if (c > kNbStage) { se += c; sn++; }
+        if (c > a.stage) { se += c; sn++; }
     }
 #pragma unroll
     for (int d = kWave / 2; d > 0; d >>= 1) {
@@ -372,6 +372,13 @@ void launch_neighbor_fill(const NbArgs &a, uint64_t spill_atoms, hipStream_t str
     if (!n) return;
     if (a.b.sorted_id32) hipLaunchKernelGGL(k_neighbor_fill<true>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(k_neighbor_fill<false>, dim3(cdiv(n, 4)), dim3(256), 0, stream, a);
+    launch_neighbor_rank_spill(a, spill_atoms, stream);
+}
+
+// the entries of the `spill_atoms` lists whose keys the fill kernel left in a.spill (k_within_fill of within.hip too: the
+// ranking writes (float bits of NbKey::thr, idx), and that run stores d^2 as thr)
+void launch_neighbor_rank_spill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream)
+{
     if (spill_atoms)
         hipLaunchKernelGGL(k_neighbor_rank_spill, dim3((uint32_t)std::min<uint64_t>(spill_atoms, 4096)), dim3(256), 0, stream, a,
                            (uint32_t)spill_atoms);

@@ -12,7 +12,8 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import ATOM_DTYPE, NEIGHBOR_DTYPE, DeviceBatch, RsasaError, Timings, check, ptr
+from ._capi import (ATOM_DTYPE, NEIGHBOR_DTYPE, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings,
+                    check, ptr)
 
 
 def device_count() -> int:
@@ -66,6 +67,18 @@ def _labels(groups, n):
     if g.dtype != np.uint32 and g.size and (int(g.min()) < 0 or int(g.max()) > 0xFFFFFFFF):
         raise ValueError("group labels must lie in [0, 2^32)")
     return np.ascontiguousarray(g, dtype=np.uint32)
+
+
+def _flag_bytes(flags, n):
+    """The flag bytes of half_sphere_exposure / atoms_within as a contiguous uint8 array of n entries, or None."""
+    if flags is None:
+        return None
+    f = np.asarray(flags)
+    if f.dtype.kind not in "ui" or f.shape != (n,):
+        raise ValueError(f"flags must be a 1-D array of {n} integer entries (uint8, one per atom)")
+    if f.dtype != np.uint8 and f.size and (int(f.min()) < 0 or int(f.max()) > 0xFF):
+        raise ValueError("flags must lie in [0, 256)")
+    return np.ascontiguousarray(f, dtype=np.uint8)
 
 
 def _out_buffer(name, buf, n):
@@ -384,13 +397,7 @@ class Context:
             dirs = _f32(dirs)
             if dirs.shape != (n, 3):
                 raise ValueError(f"dirs must be an array of shape ({n}, 3) (one direction per atom)")
-        if flags is not None:
-            f = np.asarray(flags)
-            if f.dtype.kind not in "ui" or f.shape != (n,):
-                raise ValueError(f"flags must be a 1-D array of {n} integer entries (uint8, one per atom)")
-            if f.dtype != np.uint8 and f.size and (int(f.min()) < 0 or int(f.max()) > 0xFF):
-                raise ValueError("flags must lie in [0, 256)")
-            flags = np.ascontiguousarray(f, dtype=np.uint8)
+        flags = _flag_bytes(flags, n)
         up, down = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         self._check(entry(probe_radius, ptr(dirs), ptr(flags), cutoff, ptr(up), ptr(down)))
         return up, down
@@ -410,6 +417,42 @@ class Context:
         """rsasa_half_sphere_exposure_batch: half_sphere_exposure of every structure (one grid each, atoms of other
         structures never count), rows in batch order."""
         return self._half_sphere_exposure(x, y, z, radius, ids, probe_radius, dirs, flags, cutoff, structure_offsets)
+
+    # ---- atoms within a cutoff (the lists behind the half-sphere counts) ----
+    def _atoms_within(self, x, y, z, radius, ids, probe_radius, flags, cutoff, upper_only, structure_offsets=_SINGLE):
+        (x, *_), entry = self._entry("atoms_within", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        flags = _flag_bytes(flags, n)
+        cutoff = float(cutoff)
+        if not (cutoff >= 0.0) or np.isinf(cutoff):
+            raise ValueError("cutoff must be finite and not negative")
+        # the first guess of the entries: all-atom lists of proteins hold about 0.2 C^3 entries (19 at 4.5 A, 93 at 8 A,
+        # 314 at 13 A), and no list is longer than the largest structure less one
+        largest = n if structure_offsets is _SINGLE else int(np.diff(_offsets("structure_offsets", structure_offsets)).max(initial=0))
+        n_centres = n if flags is None else int(np.count_nonzero(flags & WITHIN_CENTRE))
+        per_list = int(min(max(largest - 1, 0), 0.25 * cutoff ** 3 + 16.0))
+        upper = bool(upper_only)
+
+        def call(offsets, entries, cap):
+            return entry(probe_radius, ptr(flags), cutoff, int(upper), ptr(offsets), ptr(entries), cap)
+        return self._sized_call(call, n, n_centres * per_list // (2 if upper else 1), WITHIN_DTYPE)
+
+    def atoms_within(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, flags=None, cutoff: float = 8.0,
+                     upper_only: bool = False):
+        """rsasa_atoms_within: (offsets uint64[N + 1], entries WITHIN_DTYPE[total]).  The list of atom i,
+        entries[offsets[i]:offsets[i + 1]], holds the atoms j != i with WITHIN_PARTNER in flags[j] whose float32 d2 to i
+        is at most cutoff * cutoff (plain float32, as the header defines it), each as (d2, idx), ascending by (d2, idx);
+        atoms without WITHIN_CENTRE in flags[i] have an empty list.  flags None: every atom is centre and partner.
+        upper_only: only j > i (every pair once).  The list lengths are up + down of half_sphere_exposure.  radius and
+        probe_radius only fix the grid's cell size.  edge_index() and closest_pairs() turn the lists into a graph's edges
+        and into a contact map between groups of atoms."""
+        return self._atoms_within(x, y, z, radius, ids, probe_radius, flags, cutoff, upper_only)
+
+    def atoms_within_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, flags=None,
+                           cutoff: float = 8.0, upper_only: bool = False):
+        """rsasa_atoms_within_batch: atoms_within of every structure (one grid each, no list crosses structures);
+        offsets over the whole batch, idx the index within the structure."""
+        return self._atoms_within(x, y, z, radius, ids, probe_radius, flags, cutoff, upper_only, structure_offsets)
 
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
     def _contact_points(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
@@ -663,6 +706,52 @@ def pseudo_cb_directions(ca_xyz, chain_offsets) -> np.ndarray:
         ok = length > 0.0
         out[i[ok]] += d[ok] / length[ok, None]
     return out.astype(np.float32)
+
+
+def _within_pairs(offsets, entries, structure_offsets):
+    """(centre, partner) int64 batch-global atom indices of every entry of atoms_within[_batch]'s lists."""
+    off = np.asarray(offsets).astype(np.int64)
+    if off.ndim != 1 or off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("offsets must be non-decreasing from 0")
+    ent = np.asarray(entries)
+    if ent.dtype != WITHIN_DTYPE or ent.ndim != 1 or ent.shape[0] != off[-1]:
+        raise ValueError("entries must be a WITHIN_DTYPE array of offsets[-1] entries")
+    n = off.shape[0] - 1
+    centre = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
+    base = np.zeros(n, np.int64)
+    if structure_offsets is not None:
+        so = np.asarray(structure_offsets).astype(np.int64)
+        if so.ndim != 1 or so.shape[0] < 1 or so[0] != 0 or so[-1] != n or (np.diff(so) < 0).any():
+            raise ValueError("structure_offsets must be non-decreasing from 0 to the number of atoms")
+        base = so[np.searchsorted(so[1:], np.arange(n), side="right")] if n else base
+    return centre, base[centre] + ent["idx"].astype(np.int64)
+
+
+def edge_index(offsets, entries, structure_offsets=None) -> np.ndarray:
+    """The lists of atoms_within[_batch] as the edges of a graph, int64[2, E] in list order: row 0 the centre's
+    batch-global atom index, row 1 the partner's (its structure's first atom plus idx).  entries["d2"] runs beside it."""
+    return np.stack(_within_pairs(offsets, entries, structure_offsets))
+
+
+def closest_pairs(offsets, entries, labels, structure_offsets=None):
+    """(label_a int64[P], label_b int64[P], distance float32[P]): one row per ordered pair of different labels (centre's,
+    partner's) that occurs in the lists of atoms_within[_batch], sorted by (label_a, label_b); distance is the float32
+    square root of the smallest d2 between them.  labels holds an integer per atom of the batch - with the residue
+    number per atom this is the residue contact map by closest atom.  (Labels are compared as they are: give the
+    structures of a batch disjoint labels.)"""
+    centre, partner = _within_pairs(offsets, entries, structure_offsets)
+    lab = np.asarray(labels)
+    if lab.dtype.kind not in "ui" or lab.shape != (np.asarray(offsets).shape[0] - 1,):
+        raise ValueError("labels must be a 1-D array of one integer per atom")
+    lab = lab.astype(np.int64)
+    la, lb, d2 = lab[centre], lab[partner], np.asarray(entries)["d2"]
+    keep = la != lb
+    la, lb, d2 = la[keep], lb[keep], d2[keep]
+    order = np.lexsort((d2, lb, la))
+    la, lb, d2 = la[order], lb[order], d2[order]
+    first = np.ones(la.shape[0], bool)
+    first[1:] = (la[1:] != la[:-1]) | (lb[1:] != lb[:-1])
+    return la[first], lb[first], np.sqrt(d2[first].astype(np.float32))
 
 
 def default_link(radius, probe_radius: float = 1.4, n_points: int = 100) -> np.float32:
