@@ -41,7 +41,7 @@ extern "C" {
  * rsasa_group_contacts_batch; rsasa_exposure_vectors, rsasa_exposure_vectors_batch, rsasa_sas_volume;
  * rsasa_atom_depth, rsasa_atom_depth_batch; rsasa_surface_components, rsasa_surface_components_batch;
  * rsasa_half_sphere_exposure, rsasa_half_sphere_exposure_batch; rsasa_within_t, rsasa_atoms_within,
- * rsasa_atoms_within_batch. */
+ * rsasa_atoms_within_batch; RSASA_NEAREST_MAX_K, rsasa_nearest_atoms, rsasa_nearest_atoms_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -56,7 +56,7 @@ typedef enum rsasa_status {
     RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*: out_entries is NULL or holds
                                         fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
                                         the same for its row buffers; rsasa_surface_components*: for out_labels;
-                                        rsasa_atoms_within*: for its out_entries */
+                                        rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries */
 } rsasa_status;
 
 /* Mirrors `Atom` (reference src/structures/atomic.rs:13-24) without the
@@ -845,6 +845,76 @@ int rsasa_atoms_within_batch(rsasa_context_t *ctx,
                              const uint8_t *flags, float cutoff, int upper_only,
                              uint64_t *out_offsets,
                              rsasa_within_t *out_entries, size_t entries_capacity);
+
+/* ---- the k nearest atoms ------------------------------------------------ */
+
+/* WHO are the k nearest atoms of an atom, whatever their distance: the k-NN
+ * graphs of structure networks (a fixed fan-in per node: k = 16, 30, 48, 64 on
+ * CA traces or on all atoms).  A cutoff guessed for rsasa_atoms_within returns
+ * every entry inside it and still leaves surface atoms, termini and ligands
+ * short; here the reach follows the atom.
+ *
+ * Definition.  Flags, d2, eligibility and order are exactly those of
+ * rsasa_atoms_within with upper_only == 0.  Let W_i be the list
+ * rsasa_atoms_within defines for centre i at the same flags and cutoff.  Then
+ *
+ *     the list of atom i is the first min(k, |W_i|) entries of W_i.
+ *
+ * Entries are rsasa_within_t: d2 float32, unfused, idx the index within the
+ * structure, ascending by the key (bits(d2) << 32) | idx.  When several
+ * partners share the k-th d2, those with the smaller idx are kept: the result
+ * is unique and can be compared byte for byte.  An atom without
+ * RSASA_WITHIN_CENTRE has an empty list.  A NaN coordinate puts the atom in
+ * nobody's list and gives it an empty one.  A structure with fewer than k
+ * eligible partners gives shorter lists (all of them: n - 1 entries when every
+ * atom is a partner and there is no cutoff).
+ *
+ * cutoff: +inf means no cutoff (c2 = +inf: every partner whose d2 is not NaN
+ * is eligible), and a finite cutoff whose square overflows behaves the same;
+ * -0.0 is 0; NaN or a negative cutoff returns RSASA_ERR_INVALID_ARGUMENT.
+ * k: 1 <= k <= RSASA_NEAREST_MAX_K, anything else returns
+ * RSASA_ERR_INVALID_ARGUMENT, and so do NULL columns, structure_offsets that
+ * are not non-decreasing from 0, and out_offsets NULL.  radius, probe_radius
+ * and id are treated as in rsasa_atoms_within: they only fix the cell size.
+ * An infinite coordinate returns RSASA_ERR_GRID_TOO_LARGE and the context stays
+ * usable.  No atoms: RSASA_OK with out_offsets[0] = 0.
+ *
+ * Sizing, as in rsasa_atoms_within: out_offsets is always written (on success
+ * and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_entries is NULL or
+ * entries_capacity < out_offsets[n], nothing else is written and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned; the context stays usable.  A
+ * capacity of (number of centres) * k always suffices, so one call is enough.
+ * On the device the call takes 16 bytes per centre and k; a failed reservation
+ * returns RSASA_ERR_OUT_OF_MEMORY and the context stays usable.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  One
+ * sweep of the grid per centre, which ends by what it has found: no neighbour
+ * lists are built and no cutoff is guessed. */
+#define RSASA_NEAREST_MAX_K 256
+
+/* One structure: n_atoms atoms, id nullable (it plays no part).  flags:
+ * [n_atoms] or NULL; out_offsets: [n_atoms + 1]; out_entries:
+ * [entries_capacity]. */
+int rsasa_nearest_atoms(rsasa_context_t *ctx,
+                        const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms,
+                        float probe_radius,
+                        const uint8_t *flags, uint32_t k, float cutoff,
+                        uint64_t *out_offsets,
+                        rsasa_within_t *out_entries, size_t entries_capacity);
+
+/* Directory-mode form, as rsasa_atoms_within_batch: no list crosses
+ * structures; out_offsets is batch-global; idx is the index within the
+ * structure. */
+int rsasa_nearest_atoms_batch(rsasa_context_t *ctx,
+                              const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id,
+                              const uint32_t *structure_offsets, size_t n_structures,
+                              float probe_radius,
+                              const uint8_t *flags, uint32_t k, float cutoff,
+                              uint64_t *out_offsets,
+                              rsasa_within_t *out_entries, size_t entries_capacity);
 
 /* ---- contact counts ----------------------------------------------------- */
 

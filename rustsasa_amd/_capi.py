@@ -38,6 +38,7 @@ WITHIN_DTYPE = np.dtype([("d2", "<f4"), ("idx", "<u4")])
 assert WITHIN_DTYPE.itemsize == 8
 WITHIN_PARTNER = 1
 WITHIN_CENTRE = 2
+NEAREST_MAX_K = 256  # RSASA_NEAREST_MAX_K: the largest k of rsasa_nearest_atoms*
 
 
 class RsasaError(RuntimeError):
@@ -135,6 +136,10 @@ SYMBOLS = {
                                      _vp, _vp, C.c_size_t]),
     "rsasa_atoms_within_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_float,
                                            C.c_int, _vp, _vp, C.c_size_t]),
+    "rsasa_nearest_atoms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_uint32, C.c_float,
+                                      _vp, _vp, C.c_size_t]),
+    "rsasa_nearest_atoms_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_uint32,
+                                            C.c_float, _vp, _vp, C.c_size_t]),
     "rsasa_contact_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsasa_contact_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,

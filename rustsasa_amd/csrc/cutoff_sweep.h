@@ -1,5 +1,5 @@
-// The stop rule of a shell sweep (shell_sweep.h) that accepts an atom by d2 <= c2: shared by k_half_sphere (hse.hip) and by
-// k_within_count / k_within_fill (within.hip), which all evaluate, for the wave's atom i at c_i and an atom j at c_j,
+// The stop rule of a shell sweep (shell_sweep.h) that accepts an atom by d2 <= c2: shared by k_half_sphere (hse.hip), by
+// k_within_count / k_within_fill (within.hip) and by k_nearest (nearest.hip), which all evaluate, for the wave's atom i at c_i and an atom j at c_j,
 //     dx = c_j.x - c_i.x (dy, dz alike);  d2 = dx*dx + dy*dy + dz*dz      float32, unfused, left to right
 // and take j only if d2 <= c2 (whatever else they ask of j only removes atoms).  Device only, gfx950 only.
 //
@@ -17,6 +17,14 @@
 // the normal range, where the roundings are relative.  (NaN d2 is accepted for nobody, seen or not; c2 = +inf never meets
 // the rule.)  Without the margins, or when the rule is never met, the caller's sweep ends when the shells cover the grid
 // (ShCell::s_last), which is always exact.  For cutoff 13 and h = 3.3 the rule is met after shell 5.
+//
+// A bound found on the way.  k_nearest (nearest.hip) wants the k smallest keys (bits(d2) << 32) | idx among the atoms with
+// d2 <= c2 and calls the rule with b2 = min(c2, the k-th smallest d2 it holds once it holds k, else +inf) in place of c2.
+// The proof carries over word for word, being about one number compared with lim2: every unseen d2 is strictly above
+// lim2 >= b2.  If b2 = c2 no unseen atom is eligible; otherwise k held keys have d2 <= b2 < every unseen d2, so an unseen
+// atom cannot displace any of them, not even on a tie of d2 (where idx would decide).  The k-th smallest held d2 only falls
+// as the sweep goes on, and "the k-th smallest is at most lim2" is "at least k held d2 are at most lim2", which needs
+// no sort.  Without the margins the rule is never met and the whole grid is swept.
 #pragma once
 #include "shell_sweep.h"
 

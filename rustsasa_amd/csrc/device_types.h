@@ -273,6 +273,18 @@ struct WnArgs {
     uint32_t upper_only;                // nonzero: only partners with a larger index than the centre's
 };
 
+// ---- the k nearest atoms (nearest.hip, rsasa_nearest_atoms*) ----
+// The same batch, flags and rule (w.upper_only 0; w.cutoff may be +inf): per centre the first k entries of the list
+// WnArgs defines.  k_nearest writes them to a row of stride k and the row's length to w.n.counts; the neighbour runs'
+// scan and k_nearest_gather then make w.n.offsets and w.n.out (no spill: w.n.stage = k).
+struct NnArgs {
+    WnArgs w;
+    uint32_t k;                         // 1 .. kNearestMaxK (entry_checks.h)
+    const uint32_t *rank;               // [n_atoms], input order, or null: the row of a centre - the number of centres
+                                        // before it (a host prefix over the flag bytes); null: the row is the atom
+    unsigned long long *rows;           // [rows][k] the keys (d2 bits) << 32 | idx of each centre, ascending
+};
+
 // ---- contact counts (points.hip, rsasa_contact_points*) ----
 // The same lists and lattice (p.masks unused), per-entry counts out, aligned with NbArgs::out.
 struct CtArgs {
@@ -377,6 +389,10 @@ void launch_sort_flags(const HsArgs &h, hipStream_t stream);
 // (with NbArgs::stage = within_stage_capacity()); then the entries.
 void launch_within_count(const WnArgs &w, hipStream_t stream);
 void launch_within_fill(const WnArgs &w, uint64_t spill_atoms, hipStream_t stream);
+// The k nearest atoms (nearest.hip) on a binned batch with sorted flags: the rows, counts, offsets and NbInfo; then the
+// entries gathered from the rows (a count above k sets NbInfo::mismatch).
+void launch_nearest(const NnArgs &a, hipStream_t stream);
+void launch_nearest_gather(const NnArgs &a, hipStream_t stream);
 // The ranking of the long lists by itself (neighbors.hip): a.spill, a.spill_recs -> a.out, one workgroup per list.
 void launch_neighbor_rank_spill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.

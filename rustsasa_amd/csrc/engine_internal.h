@@ -471,6 +471,7 @@ struct rsasa_context {
         DeviceBuffer group, sorted, sorted_group, own, nrows, groups, buried, only, self_free;
         // half-sphere exposure: the directions and flags, the flags in cell-sorted order, the two counts per atom
         DeviceBuffer dirs, flags, sorted_flags, up, down;
+        DeviceBuffer rows;  // the k nearest atoms: a row of k keys per centre (NnArgs::rows)
     } run;
 };
 

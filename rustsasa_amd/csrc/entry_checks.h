@@ -70,4 +70,19 @@ inline const char *check_cutoff(float cutoff)
     return nullptr;
 }
 
+// The cutoff of the k nearest atoms: check_cutoff with +inf allowed (no cutoff).
+inline const char *check_nearest_cutoff(float cutoff)
+{
+    if (!(cutoff >= 0.0f)) return "cutoff must be +inf or finite, and not negative";
+    return nullptr;
+}
+
+// The k of the k nearest atoms: 1 .. RSASA_NEAREST_MAX_K, the most keys a compaction of k_nearest's staging keeps.
+constexpr uint32_t kNearestMaxK = 256;
+inline const char *check_nearest_k(uint32_t k)
+{
+    if (k < 1u || k > kNearestMaxK) return "k must be in [1, 256]";
+    return nullptr;
+}
+
 }  // namespace rsasa

@@ -1,6 +1,6 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h) and of the
 // point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts and
-// group contacts; and of the half-sphere exposure and the lists within a cutoff, which need the grid alone.  The batch's
+// group contacts; and of the half-sphere exposure, the lists within a cutoff and the k nearest atoms, which need the grid alone.  The batch's
 // grid is built by the SASA
 // path's kernels in a workspace of the context's own (rsasa_context::nb_ws; nb_grid), then neighbors.hip counts, scans and
 // fills the lists (nb_count, nb_fill).  A point run keeps the lists on the device: every family shares one prologue
@@ -585,6 +585,66 @@ int wn_run(rsasa_context *ctx, const Cols &c, float probe, const uint8_t *flags,
     return RSASA_OK;
 }
 
+// One run of the k nearest atoms: the grid alone and the flags as in wn_run, with the centres' ranks (a host prefix over
+// the flag bytes: which row a centre's keys go to) uploaded beside the columns; k_nearest sweeps once and leaves rows and
+// counts, the neighbour runs' scan and the sizing rule of nb_run follow, then k_nearest_gather and 8 bytes per entry back.
+int nn_run(rsasa_context *ctx, const Cols &c, float probe, const uint8_t *flags, uint32_t k, float cutoff,
+           uint64_t *out_offsets, rsasa_within_t *out_entries, size_t cap)
+{
+    static_assert(kNearestMaxK == RSASA_NEAREST_MAX_K, "the header's bound is the kernels' bound");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    if (c.N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    int rc;
+    rsasa_context::RunScratch &R = ctx->run;
+    hipStream_t st = ctx->stream;
+    NbHost *nh;
+    HsArgs h{};
+    NnArgs nn{};
+    NbInfo info{};
+    std::vector<uint32_t> rank;
+    size_t rows = c.N;
+    if (flags) {
+        rank.resize(c.N);
+        rows = 0;
+        for (size_t i = 0; i < c.N; i++) {
+            rank[i] = (uint32_t)rows;
+            rows += (flags[i] >> 1) & 1u;
+        }
+    }
+    if ((rc = nb_grid(ctx, c, flags ? rank.data() : nullptr, probe, __builtin_nanf(""), h.b)) ||
+        (rc = hs_flags(ctx, c.N, flags, h)) || (rc = reserve(ctx, R.rows, rows * k * 8)))
+        return rc;
+    nn.w.n.b = h.b;
+    if ((rc = nb_scan_buffers(ctx, c.N, k, nn.w.n))) return rc;  // (stage = k: no list is longer)
+    nn.w.sorted_flags = h.sorted_flags;
+    nn.w.cutoff = cutoff;
+    nn.w.upper_only = 0u;
+    nn.k = k;
+    nn.rank = flags ? (const uint32_t *)R.map.p : nullptr;
+    nn.rows = (unsigned long long *)R.rows.p;
+    launch_sort_flags(h, st);
+    launch_nearest(nn, st);
+    if ((rc = nb_sizes(ctx, nn.w.n, c.N, out_offsets, info))) return rc;
+    if (!out_entries || cap < info.total)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_entries is NULL or holds fewer entries than out_offsets[n]");
+    if (info.total == 0) return RSASA_OK;
+    if (info.max_k > k || info.spill_atoms) return fail(ctx, RSASA_ERR_INTERNAL, "a list of the k nearest atoms is longer than k");
+    if ((rc = reserve(ctx, R.entries, info.total * 8))) return rc;
+    nn.w.n.out = (uint2 *)R.entries.p;
+    launch_nearest_gather(nn, st);
+    nh = static_cast<NbHost *>(ctx->nb_host.p);
+    RS_HIP(ctx, hipMemcpyAsync(&nh->info, nn.w.n.info, sizeof(NbInfo), hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipMemcpyAsync(out_entries, nn.w.n.out, info.total * 8, hipMemcpyDeviceToHost, st));
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    if (nh->info.mismatch) return fail(ctx, RSASA_ERR_INTERNAL, "the rows of the k nearest atoms disagree with their counts");
+    return RSASA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -780,6 +840,35 @@ int rsasa_atoms_within_batch(rsasa_context_t *ctx, const float *x, const float *
     RS_ARGS(ctx, check_cutoff(cutoff));
     return wn_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, flags, cutoff,
                   upper_only, out_offsets, out_entries, entries_capacity);
+}
+
+int rsasa_nearest_atoms(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms, float probe_radius, const uint8_t *flags, uint32_t k, float cutoff,
+                        uint64_t *out_offsets, rsasa_within_t *out_entries, size_t entries_capacity)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    RS_ARGS(ctx, check_columns(n_atoms, x, y, z, radius, out_offsets));
+    RS_ARGS(ctx, check_nearest_k(k));
+    RS_ARGS(ctx, check_nearest_cutoff(cutoff));
+    return nn_run(ctx, Cols(x, y, z, radius, id, n_atoms), probe_radius, flags, k, cutoff, out_offsets, out_entries,
+                  entries_capacity);
+}
+
+int rsasa_nearest_atoms_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                              const uint8_t *flags, uint32_t k, float cutoff, uint64_t *out_offsets,
+                              rsasa_within_t *out_entries, size_t entries_capacity)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    size_t N;
+    RS_ARGS(ctx, check_offsets(structure_offsets, n_structures, N));
+    RS_ARGS(ctx, check_columns(N, x, y, z, radius, out_offsets));
+    RS_ARGS(ctx, check_nearest_k(k));
+    RS_ARGS(ctx, check_nearest_cutoff(cutoff));
+    return nn_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, flags, k, cutoff,
+                  out_offsets, out_entries, entries_capacity);
 }
 
 // No context, no device: double arithmetic in atom order on the host.

@@ -16,7 +16,8 @@
 //                    (neighbors.hip: one workgroup per list, 256-key tiles, any length; it writes (bits of thr, idx),
 //                    which here is the entry).  Its cost is quadratic in the length; it is the route of the exception.
 //
-// The count and the fill pass run ONE function, wn_sweep, whose decisions come from ONE rule, wn_accept, and which stops
+// The count and the fill pass run ONE function, wn_sweep, whose decisions come from ONE rule, wn_accept (within_keys.h,
+// with the sort wn_sort: k_nearest of nearest.hip shares both), and which stops
 // by ONE stop rule, sh_cutoff_reached (cutoff_sweep.h: the proof that no unseen atom can be accepted carries over from
 // k_half_sphere unchanged, the acceptance having the same d2 <= c2; upper_only only removes entries).  A fill that
 // accepted another number than the count sets NbInfo::mismatch and the host answers RSASA_ERR_INTERNAL; every write is
@@ -37,35 +38,12 @@
 // Resources (compiler's report): k_within_count 64 VGPRs, 4 096 bytes of LDS, 8 waves per SIMD; k_within_fill 83 VGPRs,
 // 36 864 bytes of LDS, 4 waves per SIMD = 16 per CU (the LDS sets it); no scratch in either.
 // Compiled with -ffp-contract=off: d2 is not fused (the definition is the model's plain float32 arithmetic).
-#include "cutoff_sweep.h"
+#include "within_keys.h"
 
 namespace rsasa {
 namespace {
 
 constexpr uint32_t kWnStage = 1024;  // keys a wave stages and sorts in LDS; longer lists go through global scratch
-
-struct WnAtom {  // the wave's atom: its cell-sorted position and input index, its centre, and the run's rule
-    uint32_t p, orig;
-    float4 me;
-    float c2;
-    bool upper;
-};
-
-// THE acceptance rule (include/rustsasa_amd.h, rsasa_atoms_within), used by both passes: the atom at cell-sorted
-// position q is in the list of the wave's atom when it is another atom, a partner, d2 <= c2 and, under upper_only, its
-// input index is the larger one (atoms of one structure: the same order as their indices within it).  orig_q: q's
-// input index when `want_orig` (the fill pass, and every pass under upper_only), else 0.
-__device__ __forceinline__ bool wn_accept(const WnArgs &a, const WnAtom &at, uint32_t q, bool want_orig, float &d2,
-                                          uint32_t &orig_q)
-{
-    const BatchView &b = a.n.b;
-    const float4 o = b.sorted_xyzr[q];
-    const uint32_t fl = a.sorted_flags[q];
-    orig_q = want_orig ? b.sorted_orig[q] : 0u;
-    const float dx = o.x - at.me.x, dy = o.y - at.me.y, dz = o.z - at.me.z;
-    d2 = dx * dx + dy * dy + dz * dz;
-    return q != at.p && (fl & 1u) != 0u && d2 <= at.c2 && (!at.upper || orig_q > at.orig);
-}
 
 // THE sweep of the centre at cell-sorted position p (input index orig), used by both passes; returns the number of
 // atoms accepted (the same in every lane).  FILL: the accepted atoms' keys go, in the order the sweep meets them, to
@@ -138,30 +116,6 @@ __global__ __launch_bounds__(256) void k_within_count(WnArgs a)
     }
     const uint32_t k = wn_sweep<false>(a, p, orig, s_excl[w], s_start[w], 0u, false, nullptr, nullptr);
     if (lane == 0) a.n.counts[orig] = k;
-}
-
-// The wave's n <= kWnStage keys in s_key, ascending: padded with all-ones keys to a power of two and sorted by the bitonic
-// network (see the head of the file).  One wave; the keys of the caller's earlier writes need no fence of the caller's.
-__device__ __forceinline__ void wn_sort(unsigned long long *s_key, uint32_t n)
-{
-    const uint32_t lane = lane_id();
-    uint32_t P = 2;
-    while (P < n) P <<= 1;
-    for (uint32_t i = n + lane; i < P; i += kWave) s_key[i] = ~0ull;
-    for (uint32_t size = 2; size <= P; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-            wave_lds_fence();
-            for (uint32_t t = lane; t < P / 2u; t += kWave) {
-                const uint32_t i = ((t & ~(stride - 1u)) << 1) | (t & (stride - 1u)), j = i | stride;
-                const unsigned long long x = s_key[i], y = s_key[j];
-                if ((x > y) == ((i & size) == 0u)) {  // ascending where bit `size` of i is clear (always, in the last merge)
-                    s_key[i] = y;
-                    s_key[j] = x;
-                }
-            }
-        }
-    }
-    wave_lds_fence();
 }
 
 __global__ __launch_bounds__(256) void k_within_fill(WnArgs a)

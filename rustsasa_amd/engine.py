@@ -12,8 +12,8 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import (ATOM_DTYPE, NEIGHBOR_DTYPE, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings,
-                    check, ptr)
+from ._capi import (ATOM_DTYPE, NEAREST_MAX_K, NEIGHBOR_DTYPE, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch,
+                    RsasaError, Timings, check, ptr)
 
 
 def device_count() -> int:
@@ -454,6 +454,40 @@ class Context:
         offsets over the whole batch, idx the index within the structure."""
         return self._atoms_within(x, y, z, radius, ids, probe_radius, flags, cutoff, upper_only, structure_offsets)
 
+    # ---- the k nearest atoms (the lists within a cutoff, cut at k; the reach follows the atom) ----
+    def _nearest_atoms(self, x, y, z, radius, ids, probe_radius, k, flags, cutoff, structure_offsets=_SINGLE):
+        (x, *_), entry = self._entry("nearest_atoms", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        flags = _flag_bytes(flags, n)
+        if isinstance(k, (bool, float)) or int(k) != k or not 1 <= int(k) <= NEAREST_MAX_K:
+            raise ValueError(f"k must be an integer in [1, {NEAREST_MAX_K}]")
+        k = int(k)
+        cutoff = float("inf") if cutoff is None else float(cutoff)
+        if not cutoff >= 0.0:
+            raise ValueError("cutoff must be None (no cutoff), +inf or finite, and not negative")
+        n_centres = n if flags is None else int(np.count_nonzero(flags & WITHIN_CENTRE))
+        cap = n_centres * k  # (always suffices: one call)
+        offsets = np.zeros(n + 1, np.uint64)
+        entries = np.empty(cap, WITHIN_DTYPE)
+        self._check(entry(probe_radius, ptr(flags), k, cutoff, ptr(offsets), ptr(entries), cap))
+        return offsets, entries[:int(offsets[-1])]
+
+    def nearest_atoms(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, k: int = 16, flags=None, cutoff=None):
+        """rsasa_nearest_atoms: (offsets uint64[N + 1], entries WITHIN_DTYPE[total]).  The list of atom i is the list
+        atoms_within defines for it at the same flags and cutoff (upper_only off), cut at k: its first
+        min(k, length) entries, ascending by (d2, idx) - the k nearest partners, those with the smaller idx where several
+        share the k-th d2.  cutoff None: no cutoff (+inf), whatever the distance.  1 <= k <= NEAREST_MAX_K.  Atoms
+        without WITHIN_CENTRE in flags[i] have an empty list; flags None: every atom is centre and partner.  radius and
+        probe_radius only fix the grid's cell size.  edge_index() and closest_pairs() work on the result as on
+        atoms_within's; nearest_table() gives the dense [N, k] form."""
+        return self._nearest_atoms(x, y, z, radius, ids, probe_radius, k, flags, cutoff)
+
+    def nearest_atoms_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, k: int = 16,
+                            flags=None, cutoff=None):
+        """rsasa_nearest_atoms_batch: nearest_atoms of every structure (one grid each, no list crosses structures);
+        offsets over the whole batch, idx the index within the structure."""
+        return self._nearest_atoms(x, y, z, radius, ids, probe_radius, k, flags, cutoff, structure_offsets)
+
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
     def _contact_points(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -731,6 +765,24 @@ def edge_index(offsets, entries, structure_offsets=None) -> np.ndarray:
     """The lists of atoms_within[_batch] as the edges of a graph, int64[2, E] in list order: row 0 the centre's
     batch-global atom index, row 1 the partner's (its structure's first atom plus idx).  entries["d2"] runs beside it."""
     return np.stack(_within_pairs(offsets, entries, structure_offsets))
+
+
+def nearest_table(offsets, entries, k: int, structure_offsets=None):
+    """The lists of nearest_atoms[_batch] as a dense table, (idx int64[N, k], d2 float32[N, k]): row i holds atom i's
+    list in order, idx as batch-global atom indices (the structure's first atom plus idx), padded with -1, and d2 padded
+    with +inf - the fixed fan-in form graph code wants.  A list longer than k raises."""
+    centre, partner = _within_pairs(offsets, entries, structure_offsets)
+    n = np.asarray(offsets).shape[0] - 1
+    k = int(k)
+    off = np.asarray(offsets).astype(np.int64)
+    if k < 1 or (n and int(np.diff(off).max()) > k):
+        raise ValueError("k must be at least 1 and no list may be longer than k")
+    col = np.arange(len(centre), dtype=np.int64) - off[centre]
+    idx = np.full((n, k), -1, np.int64)
+    d2 = np.full((n, k), np.inf, np.float32)
+    idx[centre, col] = partner
+    d2[centre, col] = np.asarray(entries)["d2"]
+    return idx, d2
 
 
 def closest_pairs(offsets, entries, labels, structure_offsets=None):
