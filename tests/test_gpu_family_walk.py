@@ -1,12 +1,15 @@
-"""The seven families that share one host prologue and one set of scratch buffers (neighbors.cpp: neighbour lists,
-accessible points, exposure vectors, atom depth, surface components, contact counts, group contacts), walked in an order
-that makes every shared buffer grow, be reused while oversized, and serve another family than the one that sized it.
+"""The ten families that share one host prologue and one set of scratch buffers (neighbors.cpp: neighbour lists,
+accessible points, exposure vectors, atom depth, surface components, contact counts, group contacts, half-sphere
+exposure, atoms within a cutoff, nearest atoms - the last three add the flags, directions, counts and rows to the scratch
+and keep the centres' ranks in the neighbour runs' map), walked in an order that makes every shared buffer grow, be
+reused while oversized, and serve another family than the one that sized it.
 What the per-family suites cannot see: a first call on a fresh context whose every list is empty (no fill has ever run,
 the entries' buffer does not exist yet), and a result that depends on which family ran before.
 
 Inputs: A one atom (its list is empty), B the 1jcd fixture, C a batch of A, an empty structure and B.  Every result of
 the walk is compared byte for byte with the same call on a context that made no other call; B is also compared with the
-Python models (points, depth, components), so the comparison is not only the library against itself."""
+Python models (points, depth, components, half-sphere counts, within-lists, nearest lists), so the comparison is not only
+the library against itself."""
 import functools
 
 import numpy as np
@@ -15,14 +18,20 @@ import pytest
 import components_model as cm
 import depth_model as dm
 import exposure_model as em
+import hse_cases as hc
+import hse_model as hm
 import nb_helpers as nh
+import nearest_model as nm
 import points_model as pm
+import within_model as wm
 
 pytestmark = pytest.mark.gpu
 
 PROBE = 1.4
 N_POINTS = (100, 129)  # 4 mask words, 4 points past the fused 96; 5 words, the last holding the one point past the fused 128
-ORDER = ("points", "groups", "depth", "contacts", "components", "exposure", "neighbours")
+ORDER = ("points", "groups", "depth", "contacts", "components", "exposure", "neighbours", "hse", "within", "nearest")
+CUTOFF_TRIO = ("hse", "within", "nearest")   # n_points is ignored
+HSE_CUTOFF, WITHIN_CUTOFF, NEAREST_K = 13.0, 8.0, 16
 
 
 @functools.lru_cache(maxsize=None)
@@ -43,6 +52,11 @@ def _link(r, n_points):
     return rustsasa_amd.default_link(r, PROBE, n_points)
 
 
+@functools.lru_cache(maxsize=None)
+def _dirs(n):
+    return hc.random_dirs(n, 83)
+
+
 def _call(ctx, family, inp, n_points):
     """The family's call on `inp` (the single-structure method, or the batch method when the input has offsets) as a
     tuple of arrays."""
@@ -51,6 +65,15 @@ def _call(ctx, family, inp, n_points):
     cols = (x, y, z, r, ids)
     if family == "neighbours":
         return ctx.precompute_neighbors_batch(*cols, so, PROBE) if batch else ctx.precompute_neighbors(*cols, PROBE)
+    if family == "hse":
+        tail = (PROBE, _dirs(len(x)), None, HSE_CUTOFF)
+        return ctx.half_sphere_exposure_batch(*cols, so, *tail) if batch else ctx.half_sphere_exposure(*cols, *tail)
+    if family == "within":
+        tail = (PROBE, None, WITHIN_CUTOFF)
+        return ctx.atoms_within_batch(*cols, so, *tail) if batch else ctx.atoms_within(*cols, *tail)
+    if family == "nearest":
+        tail = (PROBE, NEAREST_K)
+        return ctx.nearest_atoms_batch(*cols, so, *tail) if batch else ctx.nearest_atoms(*cols, *tail)
     if family == "groups":
         tail = (PROBE, n_points)
         return ctx.group_contacts_batch(*cols, groups, so, *tail) if batch else ctx.group_contacts(*cols, groups, *tail)
@@ -95,6 +118,14 @@ def test_first_call_on_a_fresh_context_has_only_empty_lists(alone, family):
     if family == "neighbours":
         offsets, entries = got
         assert np.array_equal(offsets, none) and entries.shape == (0,)
+        return
+    if family == "hse":
+        up, down = got
+        assert up.dtype == down.dtype == np.uint32 and up.tolist() == [0] and down.tolist() == [0]
+        return
+    if family in ("within", "nearest"):
+        offsets, entries = got
+        assert np.array_equal(offsets, none) and entries.shape == (0,) and entries.dtype == wm.WITHIN_DTYPE
         return
     assert got[-1].tobytes() == sasa.tobytes()
     if family == "points":
@@ -151,3 +182,10 @@ def test_fixture_equals_the_models(alone, n_points):
     offsets, labels, free, _ = alone[("components", "B", n_points)]
     want_off, want_labels, _ = cm.components(x, y, z, r, ids, PROBE, n_points, _link(r, n_points), mask=mask)
     assert np.array_equal(free, free_want) and np.array_equal(offsets, want_off) and np.array_equal(labels, want_labels)
+    up, down = alone[("hse", "B", n_points)]
+    want_up, want_down = hm.counts(x, y, z, _dirs(len(x)), None, HSE_CUTOFF)
+    assert up.tobytes() == want_up.tobytes() and down.tobytes() == want_down.tobytes() and up.any() and down.any()
+    within = wm.lists(x, y, z, None, WITHIN_CUTOFF)
+    assert _same(alone[("within", "B", n_points)], within)
+    assert _same(alone[("nearest", "B", n_points)], nm.truncate(*wm.lists(x, y, z, None, float("inf")), NEAREST_K))
+    assert wm.lengths(within[0]).max() > NEAREST_K
