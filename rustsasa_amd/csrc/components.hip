@@ -34,6 +34,8 @@
 // (S - 2.5) h >= link: a quarter cell more than link * link (one float32 product) can reach, S = 3 for link <= h / 2, S = 4
 // up to 1.5 h.  Where the margins do not hold, or S reaches the last shell that holds a cell of the grid, the whole grid
 // is swept, which is exact for any input.
+// k_component_link writes the loops of sh_sweep (shell_sweep.h: the driver and its contract) out, and must follow a change
+// there by hand: run by the driver it measured 9 % slower at the same registers (profiles/sweep_driver_ab.txt).
 // Compiled with -ffp-contract=off: q and d2 are not fused (the definition is the model's plain float32 arithmetic).
 #include "shell_sweep.h"
 

@@ -1,5 +1,6 @@
-// The stop rule of a shell sweep (shell_sweep.h) that accepts an atom by d2 <= c2: shared by k_half_sphere (hse.hip), by
-// k_within_count / k_within_fill (within.hip) and by k_nearest (nearest.hip), which all evaluate, for the wave's atom i at c_i and an atom j at c_j,
+// The stop rule of a shell sweep (sh_sweep of shell_sweep.h) that accepts an atom by d2 <= c2: shared by k_half_sphere
+// (hse.hip), by k_within_count / k_within_fill (within.hip) and by k_nearest (nearest.hip), which hand it to the driver
+// as their `after` and all evaluate, for the wave's atom i at c_i and an atom j at c_j,
 //     dx = c_j.x - c_i.x (dy, dz alike);  d2 = dx*dx + dy*dy + dz*dz      float32, unfused, left to right
 // and take j only if d2 <= c2 (whatever else they ask of j only removes atoms).  Device only, gfx950 only.
 //

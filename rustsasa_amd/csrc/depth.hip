@@ -18,6 +18,10 @@
 // product and square: rounding far below the 0.75 h between the two bounds): every unseen key is strictly larger than the
 // one held, ties included.  Without the margins the sweep ends when the shells cover the grid, which is always exact.
 // No per-candidate bound (|c_i - c_j| - R_j) and no per-cell summary of the dots were built: see DESIGN 5g.
+// The kernel takes its atom from sh_frame and writes the loops of sh_sweep (shell_sweep.h: the driver and its contract)
+// out, and must follow a change there by hand: run by the driver it measured 3.6 to 4.7 % slower at the same registers
+// (profiles/sweep_driver_ab.txt).
+// Resources (compiler's report): k_atom_depth 79 VGPRs, 12 288 bytes of LDS, 6 waves per SIMD; no scratch.
 // Compiled with -ffp-contract=off: q and d2 are not fused (the definition is the model's plain float32 arithmetic).
 #include "shell_sweep.h"
 
@@ -45,17 +49,15 @@ __global__ __launch_bounds__(256) void k_atom_depth(DpArgs d)
     const uint32_t w = threadIdx.x / kWave, lane = lane_id();
     const uint32_t p = blockIdx.x * 4u + w;
     if (p >= b.n_atoms) return;
-    const StructGrid g = b.grids[b.sid_sorted[p]];
-    const float4 me = b.sorted_xyzr[p];
-    const ShCell cell = sh_cell(g, me);
-    const bool margins = sh_margins_hold(g, b.probe);
+    const ShFrame fr = sh_frame(b, p);
+    const float4 me = fr.me;
     const uint32_t n_chunks = (a.n_points + kWave - 1) / kWave;
 
     unsigned long long best = ~0ull;  // this lane's smallest key; after a shell, the wave's
     for (uint32_t s = 0;; s++) {
-        const ShShell shell = sh_shell(g, cell, s);
+        const ShShell shell = sh_shell(fr.g, fr.cell, s);
         for (unsigned long long r0 = 0; r0 < shell.n_rows; r0 += kWave) {
-            const uint32_t total = sh_step_runs(b, g, cell, shell, s, r0, s_excl[w], s_start[w]);
+            const uint32_t total = sh_step_runs(b, fr.g, fr.cell, shell, s, r0, s_excl[w], s_start[w]);
             for (uint32_t f0 = 0; f0 < total; f0 += kWave) {
                 // ---- lanes over the atoms of the runs: those with accessible points are staged
                 const uint32_t f = f0 + lane;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(256) void k_atom_depth(DpArgs d)
                     orig = b.sorted_orig[q];
                     keep = d.free[orig] != 0u;
                 }
-                const uint32_t n_staged = sh_stage(b, keep, q, make_uint2(orig, orig - g.atom_begin), s_atom[w], s_who[w]);
+                const uint32_t n_staged = sh_stage(b, keep, q, make_uint2(orig, orig - fr.g.atom_begin), s_atom[w], s_who[w]);
                 if (n_staged == 0u) continue;  // (the same in every lane)
                 // ---- lanes over the points, 64 at a time
                 for (uint32_t c = 0; c < n_chunks; c++) {
@@ -97,9 +99,9 @@ __global__ __launch_bounds__(256) void k_atom_depth(DpArgs d)
             }
         }
         best = dp_wave_min(best);
-        if (s >= cell.s_last) break;  // the shells cover the grid
-        if (margins && s >= 2u && best != ~0ull) {
-            const float lim = (float)(s - 2u) * g.cell_size;
+        if (s >= fr.cell.s_last) break;  // the shells cover the grid
+        if (fr.margins && s >= 2u && best != ~0ull) {
+            const float lim = (float)(s - 2u) * fr.g.cell_size;
             if (__uint_as_float((uint32_t)(best >> 32)) <= lim * lim) break;
         }
     }

@@ -8,8 +8,8 @@
 //                   behind an s_waitcnt vmcnt(0) for the sorted_orig load in every trip of the inner loop - two memory
 //                   latencies in a row where the copy issues its byte load and its coordinate load together -, at the same
 //                   66 VGPRs, and a null `flags` is a branch there.
-//   k_half_sphere   one wave per cell-sorted atom i, over the shell sweep of shell_sweep.h; a wave whose atom is no centre
-//                   writes 0 / 0 and returns.  Lanes go over the atoms of a step's runs, 64 at a time; each lane reads
+//   k_half_sphere   one wave per cell-sorted atom i, run by sh_sweep (shell_sweep.h: the driver and its contract); a wave
+//                   whose atom is no centre writes 0 / 0 and returns.  Its `visit`: each lane with an atom reads
 //                   sorted_xyzr[q] and the flag byte and evaluates the definition (include/rustsasa_amd.h) -
 //                   dx = c_j.x - c_i.x; d2 = dx*dx + dy*dy + dz*dz; side = dx*u.x + dy*u.y + dz*u.z, float32, unfused, left
 //                   to right; j counts iff q != p, bit 0, d2 <= c2 - and the wave adds the popcounts of the ballots of
@@ -17,8 +17,10 @@
 //                   read by one lane, once, and used for ten operations, so a staged copy would be written and read back
 //                   for nothing (k_atom_depth stages because every staged atom meets every point of the lattice).
 //
-// The reach.  The sweep stops after shell s >= 1 once c2 <= ((s - 1/2) h)^2, or when the shells cover the grid: the rule, and
-// the proof that no unseen atom can count, ties included, are in cutoff_sweep.h (within.hip sweeps by the same rule).
+// The reach.  Its `after` is sh_cutoff_reached: the sweep stops after shell s >= 1 once c2 <= ((s - 1/2) h)^2, or when the
+// shells cover the grid: the rule, and the proof that no unseen atom can count, ties included, are in cutoff_sweep.h
+// (within.hip sweeps by the same rule).
+// Resources (compiler's report): k_half_sphere 66 VGPRs, 4 096 bytes of LDS, 7 waves per SIMD; no scratch.
 // Compiled with -ffp-contract=off: d2 and side are not fused (the definition is the model's plain float32 arithmetic).
 #include "cutoff_sweep.h"
 
@@ -47,10 +49,8 @@ __global__ __launch_bounds__(256) void k_half_sphere(HsArgs a)
         }
         return;
     }
-    const StructGrid g = b.grids[b.sid_sorted[p]];
-    const float4 me = b.sorted_xyzr[p];
-    const ShCell cell = sh_cell(g, me);
-    const bool margins = sh_margins_hold(g, b.probe);
+    const ShFrame fr = sh_frame(b, p);
+    const float4 me = fr.me;
     const bool has_dirs = a.dirs != nullptr;
     float ux = 0.0f, uy = 0.0f, uz = 0.0f;
     if (has_dirs) {
@@ -61,30 +61,23 @@ __global__ __launch_bounds__(256) void k_half_sphere(HsArgs a)
     const float c2 = a.cutoff * a.cutoff;
 
     uint32_t up = 0, down = 0;
-    for (uint32_t s = 0;; s++) {
-        const ShShell shell = sh_shell(g, cell, s);
-        for (unsigned long long r0 = 0; r0 < shell.n_rows; r0 += kWave) {
-            const uint32_t total = sh_step_runs(b, g, cell, shell, s, r0, s_excl[w], s_start[w]);
-            for (uint32_t f0 = 0; f0 < total; f0 += kWave) {
-                const uint32_t f = f0 + lane;
-                bool counts = false, above = false;
-                if (f < total) {
-                    const uint32_t q = sh_pos(s_excl[w], s_start[w], f);
-                    const float4 o = b.sorted_xyzr[q];
-                    const uint32_t fl = a.sorted_flags[q];
-                    const float dx = o.x - me.x, dy = o.y - me.y, dz = o.z - me.z;
-                    const float d2 = dx * dx + dy * dy + dz * dz;
-                    const float side = has_dirs ? dx * ux + dy * uy + dz * uz : 0.0f;
-                    counts = q != p && (fl & 1u) != 0u && d2 <= c2;
-                    above = side >= 0.0f;
-                }
-                up += (uint32_t)__popcll(ballot64(counts && above));
-                down += (uint32_t)__popcll(ballot64(counts && !above));
+    sh_sweep(
+        b, fr, s_excl[w], s_start[w],
+        [&](bool in, uint32_t q) {
+            bool counts = false, above = false;
+            if (in) {
+                const float4 o = b.sorted_xyzr[q];
+                const uint32_t fl = a.sorted_flags[q];
+                const float dx = o.x - me.x, dy = o.y - me.y, dz = o.z - me.z;
+                const float d2 = dx * dx + dy * dy + dz * dz;
+                const float side = has_dirs ? dx * ux + dy * uy + dz * uz : 0.0f;
+                counts = q != p && (fl & 1u) != 0u && d2 <= c2;
+                above = side >= 0.0f;
             }
-        }
-        if (s >= cell.s_last) break;  // the shells cover the grid
-        if (sh_cutoff_reached(margins, s, g.cell_size, c2)) break;
-    }
+            up += (uint32_t)__popcll(ballot64(counts && above));
+            down += (uint32_t)__popcll(ballot64(counts && !above));
+        },
+        [&](uint32_t s, bool) { return sh_cutoff_reached(fr.margins, s, fr.g.cell_size, c2); });
     if (lane == 0) {
         a.up[orig] = up;
         a.down[orig] = down;

@@ -3,12 +3,13 @@
 // with the smallest keys (float bits of d2) << 32 | idx, whatever their distance when the cutoff is +inf.  They need the
 // cell grid of a binned batch and the flag bytes in cell-sorted order (k_sort_flags of hse.hip), as within.hip does.
 //
-//   k_nearest          one wave per cell-sorted atom i, four per workgroup, over the shell sweep of shell_sweep.h; a wave
-//                      whose atom is no centre writes count 0 and returns.  Each lane evaluates wn_accept
-//                      (within_keys.h: THE rule of rsasa_atoms_within, `upper` off) and the accepted candidates are
-//                      staged as keys in the wave's LDS staging.  At the end the staging is sorted once (wn_sort) and
-//                      the first min(k, held) keys go to the centre's row of stride k in device scratch, the row's
-//                      length to counts[input atom].
+//   k_nearest          one wave per cell-sorted atom i, four per workgroup, run by sh_sweep (shell_sweep.h: the driver
+//                      and its contract); a wave whose atom is no centre writes count 0 and returns.  Its `visit`:
+//                      each lane evaluates wn_accept (within_keys.h: THE rule of rsasa_atoms_within, `upper` off) and
+//                      the accepted candidates are staged as keys in the wave's LDS staging (compacted first when the
+//                      next 64 might not fit); its `after`: the stop rule below.  At the end the staging is sorted once
+//                      (wn_sort) and the first min(k, held) keys go to the centre's row of stride k in device scratch,
+//                      the row's length to counts[input atom].
 //   the scan           launch_neighbor_scan (neighbors.hip) turns the counts into offsets and NbInfo; NbArgs::stage = k,
 //                      so no list counts as long.  The host sizes the caller's buffer from them as every list call does.
 //   k_nearest_gather   one wave per input atom: the row's counts[atom] keys -> out[offsets[atom] ..), 64 consecutive
@@ -24,11 +25,12 @@
 // atom in eight a centre takes an eighth of the scratch.
 //
 // The stop rule.  Let b2 = min(c2, the k-th smallest staged d2 once at least k keys are held, else +inf).  After shell s
-// the sweep stops when s >= s_last (the shells cover the grid) or sh_cutoff_reached(margins, s, h, b2) holds: by the
-// proof in cutoff_sweep.h every unseen atom has d2 strictly above lim2 >= b2, so it is outside the cutoff or cannot
-// displace any of the k held keys, not even on a tie of d2.  No sort is needed for it: "the k-th smallest d2 meets the
-// rule" is "at least k staged keys meet it" (the rule is monotone in its c2), one counting pass over the staging with
-// a ballot (nn_kth_reached), run only when c2 itself does not meet the rule and at least k keys are held.
+// the sweep stops when the shells cover the grid (the driver's `last`: nothing is counted then) or
+// sh_cutoff_reached(margins, s, h, b2) holds: by the proof in cutoff_sweep.h every unseen atom has d2 strictly above
+// lim2 >= b2, so it is outside the cutoff or cannot displace any of the k held keys, not even on a tie of d2.  No sort is
+// needed for it: "the k-th smallest d2 meets the rule" is "at least k staged keys meet it" (the rule is monotone in its
+// c2), one counting pass over the staging with a ballot (nn_kth_reached), run only when c2 itself does not meet the rule
+// and at least k keys are held.
 //
 // Staging that survives any density.  kNnStage = 1024 keys per wave, the figure of within.hip and for its reason: 8 KiB
 // per wave, 36 KiB per workgroup with the sweep's run tables, four workgroups = 16 waves per CU.  When the next batch of
@@ -82,46 +84,39 @@ __global__ __launch_bounds__(256) void k_nearest(NnArgs a)
         if (lane == 0) wa.n.counts[orig] = 0u;
         return;
     }
-    const StructGrid g = b.grids[b.sid_sorted[p]];
+    const ShFrame fr = sh_frame(b, p);
     WnAtom at;
-    at.p = p;
     at.orig = orig;
-    at.me = b.sorted_xyzr[p];
     at.c2 = wa.cutoff * wa.cutoff;
     at.upper = false;
-    const ShCell cell = sh_cell(g, at.me);
-    const bool margins = sh_margins_hold(g, b.probe);
     const uint32_t k = a.k;
     unsigned long long *key = s_key[w];
 
     uint32_t held = 0;                  // keys in the staging
     unsigned long long bound = ~0ull;   // the k-th key at the last compaction: a key above it is no candidate
-    for (uint32_t s = 0;; s++) {
-        const ShShell shell = sh_shell(g, cell, s);
-        for (unsigned long long r0 = 0; r0 < shell.n_rows; r0 += kWave) {
-            const uint32_t total = sh_step_runs(b, g, cell, shell, s, r0, s_excl[w], s_start[w]);
-            for (uint32_t f0 = 0; f0 < total; f0 += kWave) {
-                if (held + kWave > kNnStage) {  // the next 64 might not fit: keep the k smallest (held > k here)
-                    wn_sort(key, held);
-                    held = k;
-                    bound = key[k - 1u];
-                }
-                const uint32_t f = f0 + lane;
-                bool acc = false;
-                float d2 = 0.0f;
-                uint32_t orig_q = 0;
-                if (f < total) acc = wn_accept(wa, at, sh_pos(s_excl[w], s_start[w], f), true, d2, orig_q);
-                const unsigned long long cand = ((unsigned long long)__float_as_uint(d2) << 32) | (orig_q - g.atom_begin);
-                acc = acc && cand <= bound;
-                const unsigned long long m = ballot64(acc);
-                if (acc) key[held + mbcnt64(m)] = cand;
-                held += (uint32_t)__popcll(m);
+    sh_sweep(
+        b, fr, s_excl[w], s_start[w],
+        [&](bool in, uint32_t q) {
+            if (held + kWave > kNnStage) {  // the next 64 might not fit: keep the k smallest (held > k here)
+                wn_sort(key, held);
+                held = k;
+                bound = key[k - 1u];
             }
-        }
-        if (s >= cell.s_last) break;  // the shells cover the grid
-        if (sh_cutoff_reached(margins, s, g.cell_size, at.c2)) break;
-        if (margins && s >= 1u && held >= k && nn_kth_reached(key, held, k, margins, s, g.cell_size)) break;
-    }
+            bool acc = false;
+            float d2 = 0.0f;
+            uint32_t orig_q = 0;
+            if (in) acc = wn_accept(wa, fr, at, q, true, d2, orig_q);
+            const unsigned long long cand = ((unsigned long long)__float_as_uint(d2) << 32) | (orig_q - fr.g.atom_begin);
+            acc = acc && cand <= bound;
+            const unsigned long long m = ballot64(acc);
+            if (acc) key[held + mbcnt64(m)] = cand;
+            held += (uint32_t)__popcll(m);
+        },
+        [&](uint32_t s, bool last) {
+            if (last) return true;  // (no count over the staging after the last shell)
+            if (sh_cutoff_reached(fr.margins, s, fr.g.cell_size, at.c2)) return true;
+            return fr.margins && s >= 1u && held >= k && nn_kth_reached(key, held, k, fr.margins, s, fr.g.cell_size);
+        });
     wn_sort(key, held);
     const uint32_t n = min(held, k);
     unsigned long long *row = a.rows + (unsigned long long)(a.rank ? a.rank[orig] : orig) * k;

@@ -1,12 +1,12 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h) and of the
 // point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts and
-// group contacts; and of the half-sphere exposure, the lists within a cutoff and the k nearest atoms, which need the grid alone.  The batch's
-// grid is built by the SASA
-// path's kernels in a workspace of the context's own (rsasa_context::nb_ws; nb_grid), then neighbors.hip counts, scans and
-// fills the lists (nb_count, nb_fill).  A point run keeps the lists on the device: every family shares one prologue
-// (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and adds its own kernels of points.hip,
-// depth.hip or components.hip and its own downloads.  Every entry point is: resolve_ctx, the argument rules of
-// entry_checks.h, a Cols, the family's run function.
+// group contacts; and of the half-sphere exposure, the lists within a cutoff and the k nearest atoms, which need the grid
+// alone.  The batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws;
+// nb_grid, and hs_grid for the runs on the grid alone), then neighbors.hip counts, scans and fills the lists (nb_count,
+// nb_fill).  A point run keeps the lists on the device: every family shares one prologue (pt_count, pt_prepare: lists
+// with the SASA path's cutoff, lattice, PtArgs) and adds its own kernels of points.hip, depth.hip or components.hip and
+// its own downloads.  Every entry point is: resolve_ctx, the argument rules of entry_checks.h, a Cols, the family's run
+// function.
 // rsasa_sas_volume is plain host arithmetic on what the exposure vectors return.  Host code only.
 #include "engine_internal.h"
 #include "entry_checks.h"
@@ -509,21 +509,26 @@ int gp_run(rsasa_context *ctx, const Cols &c, const uint32_t *group, float probe
 
 // ---- half-sphere exposure (rsasa_half_sphere_exposure*) and atoms within a cutoff (rsasa_atoms_within*) ----
 
-// The flag bytes of a run on the grid alone (flags: host, [N], nullable) beside the binned batch h.b: uploaded, with
-// room for their cell-sorted copy; k_sort_flags (launch_half_sphere, launch_sort_flags) then writes h.sorted_flags.
-int hs_flags(rsasa_context *ctx, size_t N, const uint8_t *flags, HsArgs &h)
+// The opening of a run on the grid alone: the grid into h.b (nb_grid with every structure's own largest radius:
+// max_r = NaN), then the flag bytes (flags: host, [N], nullable) beside it: uploaded, with room for their cell-sorted copy;
+// k_sort_flags (launch_half_sphere, launch_sort_flags) then writes h.sorted_flags.
+int hs_grid(rsasa_context *ctx, const Cols &c, const uint32_t *idx_map, float probe, const uint8_t *flags, HsArgs &h)
 {
     int rc;
     rsasa_context::RunScratch &R = ctx->run;
-    if ((flags && (rc = reserve(ctx, R.flags, N))) || (rc = reserve(ctx, R.sorted_flags, N))) return rc;
+    const size_t N = c.N;
+    if ((rc = nb_grid(ctx, c, idx_map, probe, __builtin_nanf(""), h.b)) || (flags && (rc = reserve(ctx, R.flags, N))) ||
+        (rc = reserve(ctx, R.sorted_flags, N)))
+        return rc;
     if (flags) RS_HIP(ctx, hipMemcpyAsync(R.flags.p, flags, N, hipMemcpyHostToDevice, ctx->stream));
     h.flags = flags ? (const uint8_t *)R.flags.p : nullptr;
     h.sorted_flags = (uint8_t *)R.sorted_flags.p;
     return RSASA_OK;
 }
 
-// One run of the half-sphere counts: the grid alone (nb_grid: no counting pass, no lists), the directions and flags
-// beside it, k_sort_flags and k_half_sphere; 8 bytes per atom come back.
+// One run of the half-sphere counts: the grid alone (hs_grid: no counting pass, no lists) with the flags, the directions
+// beside them (their buffer is reserved behind the flags', which hs_grid reserves), k_sort_flags and k_half_sphere; 8 bytes
+// per atom come back.
 int hs_run(rsasa_context *ctx, const Cols &c, float probe, const float *dirs, const uint8_t *flags, float cutoff,
            uint32_t *out_up, uint32_t *out_down)
 {
@@ -535,8 +540,8 @@ int hs_run(rsasa_context *ctx, const Cols &c, float probe, const float *dirs, co
     hipStream_t st = ctx->stream;
     const size_t N = c.N;
     HsArgs h{};
-    if ((rc = nb_grid(ctx, c, nullptr, probe, __builtin_nanf(""), h.b)) || (dirs && (rc = reserve(ctx, R.dirs, N * 12))) ||
-        (rc = hs_flags(ctx, N, flags, h)) || (rc = reserve(ctx, R.up, N * 4)) || (rc = reserve(ctx, R.down, N * 4)))
+    if ((rc = hs_grid(ctx, c, nullptr, probe, flags, h)) || (dirs && (rc = reserve(ctx, R.dirs, N * 12))) ||
+        (rc = reserve(ctx, R.up, N * 4)) || (rc = reserve(ctx, R.down, N * 4)))
         return rc;
     if (dirs) RS_HIP(ctx, hipMemcpyAsync(R.dirs.p, dirs, N * 12, hipMemcpyHostToDevice, st));
     h.dirs = dirs ? (const float *)R.dirs.p : nullptr;
@@ -567,7 +572,7 @@ int wn_run(rsasa_context *ctx, const Cols &c, float probe, const uint8_t *flags,
     HsArgs h{};
     WnArgs w{};
     NbInfo info{};
-    if ((rc = nb_grid(ctx, c, nullptr, probe, __builtin_nanf(""), h.b)) || (rc = hs_flags(ctx, c.N, flags, h))) return rc;
+    if ((rc = hs_grid(ctx, c, nullptr, probe, flags, h))) return rc;
     w.n.b = h.b;
     if ((rc = nb_scan_buffers(ctx, c.N, within_stage_capacity(), w.n))) return rc;
     w.sorted_flags = h.sorted_flags;
@@ -615,8 +620,7 @@ int nn_run(rsasa_context *ctx, const Cols &c, float probe, const uint8_t *flags,
             rows += (flags[i] >> 1) & 1u;
         }
     }
-    if ((rc = nb_grid(ctx, c, flags ? rank.data() : nullptr, probe, __builtin_nanf(""), h.b)) ||
-        (rc = hs_flags(ctx, c.N, flags, h)) || (rc = reserve(ctx, R.rows, rows * k * 8)))
+    if ((rc = hs_grid(ctx, c, flags ? rank.data() : nullptr, probe, flags, h)) || (rc = reserve(ctx, R.rows, rows * k * 8)))
         return rc;
     nn.w.n.b = h.b;
     if ((rc = nb_scan_buffers(ctx, c.N, k, nn.w.n))) return rc;  // (stage = k: no list is longer)

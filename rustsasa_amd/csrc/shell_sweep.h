@@ -1,10 +1,31 @@
-// The shell sweep that k_atom_depth (depth.hip) and k_component_link (components.hip) share (device only, gfx950 only).
+// The shell sweep of the wave-per-atom kernels that search the grid beyond the neighbour reach (device only, gfx950
+// only): its frame (sh_frame), its driver (sh_sweep) and the steps the driver is made of.  Six kernels sweep this way,
+// each with its own work per batch of atoms (the driver's `visit`) and its own stop rule (its `after`).
+// Run by sh_sweep:
+//   k_half_sphere (hse.hip)            sh_cutoff_reached(c2) of cutoff_sweep.h
+//   k_nearest (nearest.hip)            the same, or the k-th smallest staged d2 in place of c2 (nn_kth_reached)
+// With the driver's three loops written out, because run by sh_sweep they measured slower on the MI355X at the same
+// registers, LDS and (within a few) instructions - the table is profiles/sweep_driver_ab.txt; their instruction streams
+// are the ones they had before the driver existed.  A change to sh_sweep is made in these three places too:
+//   wn_sweep of k_within_count and k_within_fill (within.hip)   sh_cutoff_reached(c2); the fill 1.1 to 1.2 % slower
+//   k_atom_depth (depth.hip)           best_d2 <= ((s - 2) h)^2, after reducing `best` over the wave; 3.6 to 4.7 % slower
+//   k_component_link (components.hip)  a fixed reach, shells 0 .. s_end, computed before the sweep; 9 % slower.  It does
+//                                      not take sh_frame either: with the frame alone its listing changes (936
+//                                      instructions for 932), and that build was not timed.
 // One wave per cell-sorted atom i.  The cells of its structure's grid are swept in Chebyshev shells s = 0, 1, 2, ... around
 // its own cell: shell s is the cells at distance exactly s, cut into x-runs of cell starts as nb_runs cuts the 5x5x5 block
 // - a row (y, z) on the rim of the shell's square gives the whole run [cx - s, cx + s], a row inside it the two cells
 // cx - s and cx + s -, 64 rows at a time (sh_step_runs), both cell-start encodings (StructGrid::in_lds).  Lanes then go
-// over the atoms of the runs, 64 at a time (sh_pos), and the atoms the caller keeps are compacted into LDS (sh_stage;
+// over the atoms of the runs, 64 at a time (sh_pos), and the atoms a kernel keeps it may compact into LDS (sh_stage;
 // k_component_link writes that one step out, see there).
+//
+// The driver's contract.  sh_sweep holds the three loops (shells, steps of 64 rows, batches of 64 atoms), and every proof
+// in cutoff_sweep.h, depth.hip and components.hip rests on them being exactly this, in sh_sweep and in the three copies:
+//   - every cell of the shells 0 .. s has been visited before `after` is asked about s;
+//   - "the shells cover the grid" (s >= ShCell::s_last) is tested before the kernel's own rule and ends the sweep whatever
+//     that rule says; sh_sweep hands it to `after` as `last`, so a rule that costs something returns at once when it is set;
+//   - every lane of the wave reaches every ballot: `visit` and `after` are called by all 64 lanes, lanes without an atom
+//     included (`in` false), and no lane leaves the loops before the others.
 //
 // What an unseen atom implies.  Let h = StructGrid::cell_size = probe + max_r.  After shell s every atom j not yet seen
 // has a cell coordinate that differs from i's by more than s along some axis.  A cell coordinate is floor(t'), t' the
@@ -14,8 +35,8 @@
 // rounded sum of a radius and the probe), probe >= 0, and every |coordinate| <= 65536 h - a coordinate's ulp is at most
 // h / 128 and t' < 2^18, so t' is within 1/16 of the exact (x - min) / h, and |x_j - x_i| > (s - 1/8) h.  Every dot of j
 // lies within R_j <= h of c_j, and a dot q = c_j + R_j * s_k and a difference of two points carry a few roundings of at
-// most h / 128 each.  The stop rule of k_atom_depth and the reach of k_component_link follow from this; without the
-// margins both sweep until the shells cover the grid (ShCell::s_last), which is always exact.
+// most h / 128 each.  The stop rules of the six kernels follow from this; without the margins every one of them sweeps
+// until the shells cover the grid (ShCell::s_last), which is always exact.
 #pragma once
 #include "device_utils.h"
 
@@ -143,6 +164,49 @@ __device__ __forceinline__ uint32_t sh_stage(const BatchView &b, bool keep, uint
     }
     wave_lds_fence();
     return n_staged;
+}
+
+struct ShFrame {  // what every sweep kernel holds of the wave's atom before the sweep
+    uint32_t p;    // its cell-sorted position
+    StructGrid g;  // its structure's grid
+    float4 me;     // (c_i, r_i)
+    ShCell cell;
+    bool margins;  // sh_margins_hold
+};
+
+__device__ __forceinline__ ShFrame sh_frame(const BatchView &b, uint32_t p)
+{
+    ShFrame fr;
+    fr.p = p;
+    fr.g = b.grids[b.sid_sorted[p]];
+    fr.me = b.sorted_xyzr[p];
+    fr.cell = sh_cell(fr.g, fr.me);
+    fr.margins = sh_margins_hold(fr.g, b.probe);
+    return fr;
+}
+
+// THE sweep (the contract: the head of the file).  visit(in, q): every lane, once per batch of 64 flat positions of a
+// step's runs; `in`: the lane has an atom, q its cell-sorted position (else 0).  after(s, last): every lane, once per
+// shell, after all of its steps; last = s >= s_last; the sweep ends when `last` is set or `after` returns true.
+// s_excl, s_start: the wave's run tables (LDS, kShRuns entries each).
+template <class Visit, class After>
+__device__ __forceinline__ void sh_sweep(const BatchView &b, const ShFrame &fr, uint32_t *s_excl, uint32_t *s_start,
+                                         Visit visit, After after)
+{
+    const uint32_t lane = lane_id();
+    for (uint32_t s = 0;; s++) {
+        const ShShell shell = sh_shell(fr.g, fr.cell, s);
+        for (unsigned long long r0 = 0; r0 < shell.n_rows; r0 += kWave) {
+            const uint32_t total = sh_step_runs(b, fr.g, fr.cell, shell, s, r0, s_excl, s_start);
+            for (uint32_t f0 = 0; f0 < total; f0 += kWave) {
+                const uint32_t f = f0 + lane;
+                const bool in = f < total;
+                visit(in, in ? sh_pos(s_excl, s_start, f) : 0u);
+            }
+        }
+        const bool last = s >= fr.cell.s_last;  // the shells cover the grid
+        if (after(s, last) || last) break;
+    }
 }
 
 }  // namespace

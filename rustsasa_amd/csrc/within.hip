@@ -17,11 +17,13 @@
 //                    which here is the entry).  Its cost is quadratic in the length; it is the route of the exception.
 //
 // The count and the fill pass run ONE function, wn_sweep, whose decisions come from ONE rule, wn_accept (within_keys.h,
-// with the sort wn_sort: k_nearest of nearest.hip shares both), and which stops
-// by ONE stop rule, sh_cutoff_reached (cutoff_sweep.h: the proof that no unseen atom can be accepted carries over from
-// k_half_sphere unchanged, the acceptance having the same d2 <= c2; upper_only only removes entries).  A fill that
-// accepted another number than the count sets NbInfo::mismatch and the host answers RSASA_ERR_INTERNAL; every write is
-// bounded by the count regardless.
+// with the sort wn_sort: k_nearest of nearest.hip shares both), and which stops by ONE stop rule, sh_cutoff_reached
+// (cutoff_sweep.h: the proof that no unseen atom can be accepted carries over from k_half_sphere unchanged, the
+// acceptance having the same d2 <= c2; upper_only only removes entries).  A fill that accepted another number than the
+// count sets NbInfo::mismatch and the host answers RSASA_ERR_INTERNAL; every write is bounded by the count regardless.
+// wn_sweep takes its atom from sh_frame and writes the loops of sh_sweep (shell_sweep.h: the driver and its contract)
+// out, and must follow a change there by hand: run by the driver k_within_fill measured 1.1 to 1.2 % slower
+// (profiles/sweep_driver_ab.txt).
 //
 // The staging and the sort.  All-atom lists of proteins are 80-160 long at 8 A, 250-560 at 13 A and 330-810 at 15 A
 // (mean - maximum of the fixtures; large proteins sit near the maxima).  kWnStage = 1024 keys per wave holds every one
@@ -54,34 +56,30 @@ __device__ __forceinline__ uint32_t wn_sweep(const WnArgs &a, uint32_t p, uint32
 {
     const BatchView &b = a.n.b;
     const uint32_t lane = lane_id();
-    const StructGrid g = b.grids[b.sid_sorted[p]];
+    const ShFrame fr = sh_frame(b, p);
     WnAtom at;
-    at.p = p;
     at.orig = orig;
-    at.me = b.sorted_xyzr[p];
     at.c2 = a.cutoff * a.cutoff;
     at.upper = a.upper_only != 0u;
     const bool want_orig = FILL || at.upper;
-    const ShCell cell = sh_cell(g, at.me);
-    const bool margins = sh_margins_hold(g, b.probe);
 
     uint32_t k = 0;
     for (uint32_t s = 0;; s++) {
-        const ShShell shell = sh_shell(g, cell, s);
+        const ShShell shell = sh_shell(fr.g, fr.cell, s);
         for (unsigned long long r0 = 0; r0 < shell.n_rows; r0 += kWave) {
-            const uint32_t total = sh_step_runs(b, g, cell, shell, s, r0, s_excl, s_start);
+            const uint32_t total = sh_step_runs(b, fr.g, fr.cell, shell, s, r0, s_excl, s_start);
             for (uint32_t f0 = 0; f0 < total; f0 += kWave) {
                 const uint32_t f = f0 + lane;
                 bool acc = false;
                 float d2 = 0.0f;
                 uint32_t orig_q = 0;
-                if (f < total) acc = wn_accept(a, at, sh_pos(s_excl, s_start, f), want_orig, d2, orig_q);
+                if (f < total) acc = wn_accept(a, fr, at, sh_pos(s_excl, s_start, f), want_orig, d2, orig_q);
                 const unsigned long long m = ballot64(acc);
                 if (FILL) {
                     const uint32_t slot = k + mbcnt64(m);
                     if (acc && slot < K) {
                         const unsigned long long key =
-                            ((unsigned long long)__float_as_uint(d2) << 32) | (orig_q - g.atom_begin);
+                            ((unsigned long long)__float_as_uint(d2) << 32) | (orig_q - fr.g.atom_begin);
                         if (spill) {
                             NbKey e;
                             e.key = key;
@@ -96,8 +94,8 @@ __device__ __forceinline__ uint32_t wn_sweep(const WnArgs &a, uint32_t p, uint32
                 k += (uint32_t)__popcll(m);
             }
         }
-        if (s >= cell.s_last) break;  // the shells cover the grid
-        if (sh_cutoff_reached(margins, s, g.cell_size, at.c2)) break;
+        if (s >= fr.cell.s_last) break;  // the shells cover the grid
+        if (sh_cutoff_reached(fr.margins, s, fr.g.cell_size, at.c2)) break;
     }
     return k;
 }

@@ -9,9 +9,8 @@
 namespace rsasa {
 namespace {
 
-struct WnAtom {  // the wave's atom: its cell-sorted position and input index, its centre, and the run's rule
-    uint32_t p, orig;
-    float4 me;
+struct WnAtom {  // what the rule needs of the wave's atom beside its frame (ShFrame): its input index and the run's rule
+    uint32_t orig;
     float c2;
     bool upper;
 };
@@ -20,16 +19,16 @@ struct WnAtom {  // the wave's atom: its cell-sorted position and input index, i
 // position q is in the list of the wave's atom when it is another atom, a partner, d2 <= c2 and, under upper_only, its
 // input index is the larger one (atoms of one structure: the same order as their indices within it).  orig_q: q's
 // input index when `want_orig` (the passes that write entries, and every pass under upper_only), else 0.
-__device__ __forceinline__ bool wn_accept(const WnArgs &a, const WnAtom &at, uint32_t q, bool want_orig, float &d2,
-                                          uint32_t &orig_q)
+__device__ __forceinline__ bool wn_accept(const WnArgs &a, const ShFrame &fr, const WnAtom &at, uint32_t q, bool want_orig,
+                                          float &d2, uint32_t &orig_q)
 {
     const BatchView &b = a.n.b;
     const float4 o = b.sorted_xyzr[q];
     const uint32_t fl = a.sorted_flags[q];
     orig_q = want_orig ? b.sorted_orig[q] : 0u;
-    const float dx = o.x - at.me.x, dy = o.y - at.me.y, dz = o.z - at.me.z;
+    const float dx = o.x - fr.me.x, dy = o.y - fr.me.y, dz = o.z - fr.me.z;
     d2 = dx * dx + dy * dy + dz * dz;
-    return q != at.p && (fl & 1u) != 0u && d2 <= at.c2 && (!at.upper || orig_q > at.orig);
+    return q != fr.p && (fl & 1u) != 0u && d2 <= at.c2 && (!at.upper || orig_q > at.orig);
 }
 
 // The wave's n keys in s_key, ascending: padded with all-ones keys to P, the power of two at or above n (s_key holds at
