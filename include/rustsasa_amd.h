@@ -41,7 +41,8 @@ extern "C" {
  * rsasa_group_contacts_batch; rsasa_exposure_vectors, rsasa_exposure_vectors_batch, rsasa_sas_volume;
  * rsasa_atom_depth, rsasa_atom_depth_batch; rsasa_surface_components, rsasa_surface_components_batch;
  * rsasa_half_sphere_exposure, rsasa_half_sphere_exposure_batch; rsasa_within_t, rsasa_atoms_within,
- * rsasa_atoms_within_batch; RSASA_NEAREST_MAX_K, rsasa_nearest_atoms, rsasa_nearest_atoms_batch. */
+ * rsasa_atoms_within_batch; RSASA_NEAREST_MAX_K, rsasa_nearest_atoms, rsasa_nearest_atoms_batch;
+ * RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS, rsasa_radial_counts, rsasa_radial_counts_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -915,6 +916,115 @@ int rsasa_nearest_atoms_batch(rsasa_context_t *ctx,
                               const uint8_t *flags, uint32_t k, float cutoff,
                               uint64_t *out_offsets,
                               rsasa_within_t *out_entries, size_t entries_capacity);
+
+/* ---- radial counts ------------------------------------------------------ */
+
+/* HOW MANY atoms OF WHICH KIND AT WHICH DISTANCE an atom has around it: per
+ * centre atom the number of partner atoms of its own structure by the
+ * partner's class and by distance bin - contact numbers at several radii in one
+ * pass (6 / 8 / 10 / 12 A), element-pair or residue-type environment
+ * fingerprints (counts of C / N / O / S partners within 12 A), the local
+ * density profile - and, per structure, the same counts summed by the centre's
+ * class: the pair-distance histogram by class pair, the numerator of a radial
+ * distribution function.  One sweep of the grid per centre, as far as the last
+ * edge needs; what rsasa_half_sphere_exposure counts at one radius, split.
+ *
+ * Definition.  For a structure, each atom i has centre c_i, a flag byte f_i:
+ * bit 0 (RSASA_RADIAL_PARTNER) - the atom is a partner, it is counted; bit 1
+ * (RSASA_RADIAL_CENTRE) - the atom is a centre, it gets a row; the other bits
+ * are ignored (the bits of RSASA_HSE_PARTNER / RSASA_HSE_CENTRE) - and a class
+ * byte classes[i] < n_classes.  edges[0 .. n_bins) are the bins' outer radii.
+ * All arithmetic is float32, unfused, left to right, exactly as in
+ * rsasa_half_sphere_exposure:
+ *
+ *     e2[k] = edges[k] * edges[k]        (may overflow to +inf, underflow to 0)
+ *     dx = c_j.x - c_i.x                 (dy, dz alike)
+ *     d2 = dx * dx + dy * dy + dz * dz
+ *     j counts for i  iff  j != i, j in the SAME structure, (f_j & 1), (f_i & 2),
+ *                          d2 <= e2[n_bins - 1]
+ *     bin(i, j) = the smallest k with d2 <= e2[k]
+ *     out_counts[i][classes[j]][bin(i, j)] += 1
+ *     out_pairs[s][a][b][k] = sum over the centres i of structure s with
+ *                             classes[i] == a of out_counts[i][b][k]
+ *
+ * Bin k therefore holds the partners with e2[k - 1] < d2 <= e2[k] (bin 0: d2 <=
+ * e2[0]).  An atom without bit 1 gets an all-zero row and adds nothing to
+ * out_pairs.  flags == NULL: every atom is both a centre and a partner.
+ * classes == NULL: every atom is class 0.  A NaN coordinate makes d2 NaN: a NaN
+ * d2 counts nowhere, and that atom, as a centre, gets a zero row.  Of several
+ * equal edges the first takes the pair and the others stay empty; with
+ * edges[0] == 0, bin 0 holds exactly the coincident atoms.  e2[n_bins - 1] may
+ * overflow to +inf: then every partner whose d2 is not NaN is counted.  Atom
+ * ids play no part.  The counts are integers and have no order, so they can be
+ * checked for equality.
+ *
+ * The cumulative identity.  For every k, the sum of out_counts[i][b][k'] over
+ * every class b and every k' <= k equals out_up[i] + out_down[i] of
+ * rsasa_half_sphere_exposure at the same flags and cutoff = edges[k]; the sum
+ * over one class b alone equals that count when the partner bit is cleared on
+ * the atoms of the other classes.
+ *
+ * Symmetry.  With flags == NULL, out_pairs[s][a][b][k] == out_pairs[s][b][a][k]:
+ * d2 is the same bit pattern in both directions.  Otherwise the two are
+ * separate entries (centres of class a around which partners of class b lie,
+ * and the reverse).  A pair of two centres of one class is counted from both
+ * ends: out_pairs[s][a][a][k] is twice the number of unordered pairs.
+ *
+ * radius and probe_radius are taken, and checked by the rules of the other
+ * calls (probe_radius + largest radius a positive finite number), only because
+ * they fix the cell size of the grid; the result does not depend on them.
+ *
+ * n_classes must lie in [1, RSASA_RADIAL_MAX_CLASSES] and n_bins in
+ * [1, RSASA_RADIAL_MAX_BINS]; every edge must be finite and >= 0 (-0.0 is 0) and
+ * the edges non-decreasing (equal edges are allowed); every class byte, on any
+ * atom, centre or partner or neither, must be below n_classes - the host reads
+ * them all before anything is launched.  Anything else returns
+ * RSASA_ERR_INVALID_ARGUMENT, and so do NULL edges, NULL columns,
+ * structure_offsets that are not non-decreasing from 0, and, where there are
+ * atoms, out_counts and out_pairs both NULL (either one may be NULL: it is
+ * then not written).  An infinite coordinate returns RSASA_ERR_GRID_TOO_LARGE and
+ * the context stays usable.  No atoms: RSASA_OK, and out_pairs, when given, is
+ * zeroed for the (empty) structures.
+ *
+ * Device memory.  The call holds the dense [N][n_classes][n_bins] uint32 table
+ * on the device - 4 * n_classes * n_bins bytes per atom, 2 KiB at the bounds -
+ * even when only out_pairs is asked for: the pair tables are summed from its
+ * rows.  A failed reservation returns RSASA_ERR_OUT_OF_MEMORY and the context
+ * stays usable.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  No
+ * neighbour lists are built; 4 * n_classes * n_bins bytes per atom come back,
+ * or, with out_counts NULL, 8 * n_classes^2 * n_bins bytes per structure. */
+#define RSASA_RADIAL_PARTNER 1
+#define RSASA_RADIAL_CENTRE 2
+#define RSASA_RADIAL_MAX_CLASSES 16
+#define RSASA_RADIAL_MAX_BINS 32
+
+/* One structure: n_atoms atoms, id nullable (it plays no part).  flags, classes:
+ * [n_atoms] or NULL; edges: [n_bins]; out_counts: [n_atoms][n_classes][n_bins],
+ * row-major, or NULL; out_pairs: [n_classes][n_classes][n_bins] or NULL. */
+int rsasa_radial_counts(rsasa_context_t *ctx,
+                        const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms,
+                        float probe_radius,
+                        const uint8_t *flags, const uint8_t *classes, uint32_t n_classes,
+                        const float *edges, uint32_t n_bins,
+                        uint32_t *out_counts, uint64_t *out_pairs);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid each; an empty structure is legal, its
+ * table is zero); atoms of other structures never count.  flags, classes and
+ * out_counts run over structure_offsets[n_structures] atoms; out_pairs is
+ * [n_structures][n_classes][n_classes][n_bins]. */
+int rsasa_radial_counts_batch(rsasa_context_t *ctx,
+                              const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id,
+                              const uint32_t *structure_offsets, size_t n_structures,
+                              float probe_radius,
+                              const uint8_t *flags, const uint8_t *classes, uint32_t n_classes,
+                              const float *edges, uint32_t n_bins,
+                              uint32_t *out_counts, uint64_t *out_pairs);
 
 /* ---- contact counts ----------------------------------------------------- */
 

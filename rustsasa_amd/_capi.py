@@ -39,6 +39,8 @@ assert WITHIN_DTYPE.itemsize == 8
 WITHIN_PARTNER = 1
 WITHIN_CENTRE = 2
 NEAREST_MAX_K = 256  # RSASA_NEAREST_MAX_K: the largest k of rsasa_nearest_atoms*
+RADIAL_MAX_CLASSES = 16  # RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS: the widest row of rsasa_radial_counts*
+RADIAL_MAX_BINS = 32
 
 
 class RsasaError(RuntimeError):
@@ -140,6 +142,10 @@ SYMBOLS = {
                                       _vp, _vp, C.c_size_t]),
     "rsasa_nearest_atoms_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_uint32,
                                             C.c_float, _vp, _vp, C.c_size_t]),
+    "rsasa_radial_counts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp, C.c_uint32, _vp,
+                                      C.c_uint32, _vp, _vp]),
+    "rsasa_radial_counts_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp,
+                                            C.c_uint32, _vp, C.c_uint32, _vp, _vp]),
     "rsasa_contact_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsasa_contact_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,

@@ -3,6 +3,8 @@
 // as their `after` and all evaluate, for the wave's atom i at c_i and an atom j at c_j,
 //     dx = c_j.x - c_i.x (dy, dz alike);  d2 = dx*dx + dy*dy + dz*dz      float32, unfused, left to right
 // and take j only if d2 <= c2 (whatever else they ask of j only removes atoms).  Device only, gfx950 only.
+// k_radial_counts (radial.hip) is covered too: its acceptance is d2 <= c2 with c2 the last squared edge, e2[n_bins - 1].
+// The bin it then finds only partitions what was accepted, so nothing below depends on it.
 //
 // The reach.  In a structure that passes sh_margins_hold an atom j not seen after shell s >= 1 has, along some axis,
 // D = |x_j - x_i| > (s - 1/8) h in exact arithmetic, h = StructGrid::cell_size (shell_sweep.h, "What an unseen atom

@@ -285,6 +285,21 @@ struct NnArgs {
     unsigned long long *rows;           // [rows][k] the keys (d2 bits) << 32 | idx of each centre, ascending
 };
 
+// ---- radial counts (radial.hip, rsasa_radial_counts*) ----
+// A binned batch (no neighbour lists) with a flag byte and a class byte per atom and a list of distance bins: per centre
+// the partners of its own structure by (class, bin), and per structure the sums of those rows by the centre's class.
+struct RdArgs {
+    BatchView b;                        // the binned batch: grids, cell starts, sorted order
+    const uint8_t *flags;               // [n_atoms], input order, or null: every atom is centre and partner
+    const uint8_t *classes;             // [n_atoms], input order, or null: every atom is class 0; every byte < n_classes
+    uint8_t *sorted_kinds;              // [n_atoms] (class << 2) | (flags & 3) in cell-sorted order (k_sort_kinds)
+    const uint32_t *so;                 // [n_structures + 1] the structures' offsets in input order (k_radial_pairs)
+    uint32_t n_classes, n_bins;         // 1 .. kRadialMaxClasses, 1 .. kRadialMaxBins (entry_checks.h)
+    float e2[32];                       // [n_bins] the squared edges, edges[k] * edges[k] (one float32 product), non-decreasing
+    uint32_t *table;                    // [n_atoms][n_classes][n_bins], input order: every row is written
+    unsigned long long *pairs;          // [n_structures][n_classes][n_classes][n_bins] or null; zeroed by the caller
+};
+
 // ---- contact counts (points.hip, rsasa_contact_points*) ----
 // The same lists and lattice (p.masks unused), per-entry counts out, aligned with NbArgs::out.
 struct CtArgs {
@@ -393,6 +408,9 @@ void launch_within_fill(const WnArgs &w, uint64_t spill_atoms, hipStream_t strea
 // entries gathered from the rows (a count above k sets NbInfo::mismatch).
 void launch_nearest(const NnArgs &a, hipStream_t stream);
 void launch_nearest_gather(const NnArgs &a, hipStream_t stream);
+// The radial counts (radial.hip) on a binned batch: the kinds in cell-sorted order, every row of r.table and, with
+// r.pairs, the rows' sums added to the pair tables.
+void launch_radial(const RdArgs &r, hipStream_t stream);
 // The ranking of the long lists by itself (neighbors.hip): a.spill, a.spill_recs -> a.out, one workgroup per list.
 void launch_neighbor_rank_spill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.

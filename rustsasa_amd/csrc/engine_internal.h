@@ -472,6 +472,8 @@ struct rsasa_context {
         // half-sphere exposure: the directions and flags, the flags in cell-sorted order, the two counts per atom
         DeviceBuffer dirs, flags, sorted_flags, up, down;
         DeviceBuffer rows;  // the k nearest atoms: a row of k keys per centre (NnArgs::rows)
+        // radial counts: the class bytes, the structures' offsets, the dense table of rows, the pair tables (RdArgs)
+        DeviceBuffer classes, so, table, pairs;
     } run;
 };
 

@@ -85,4 +85,29 @@ inline const char *check_nearest_k(uint32_t k)
     return nullptr;
 }
 
+// The bins and classes of the radial counts: 1 .. RSASA_RADIAL_MAX_BINS edges, each finite and not negative (-0.0 is
+// 0), non-decreasing (equal edges are allowed), and 1 .. RSASA_RADIAL_MAX_CLASSES classes - a row of k_radial_counts'
+// histogram is n_classes * n_bins cells of LDS.
+constexpr uint32_t kRadialMaxClasses = 16, kRadialMaxBins = 32;
+inline const char *check_radial(const float *edges, uint32_t n_bins, uint32_t n_classes)
+{
+    if (n_classes < 1u || n_classes > kRadialMaxClasses) return "n_classes must be in [1, 16]";
+    if (n_bins < 1u || n_bins > kRadialMaxBins) return "n_bins must be in [1, 32]";
+    if (!edges) return "NULL argument";
+    for (uint32_t k = 0; k < n_bins; k++) {
+        if (!(edges[k] >= 0.0f) || std::isinf(edges[k])) return "edges must be finite and not negative";
+        if (k && edges[k] < edges[k - 1u]) return "edges must be non-decreasing";
+    }
+    return nullptr;
+}
+
+// The class bytes of N atoms (nullable: every atom is class 0): every one below n_classes, on any atom.
+inline const char *check_classes(const uint8_t *classes, size_t N, uint32_t n_classes)
+{
+    if (!classes) return nullptr;
+    for (size_t i = 0; i < N; i++)
+        if (classes[i] >= n_classes) return "classes must lie below n_classes";
+    return nullptr;
+}
+
 }  // namespace rsasa

@@ -1,7 +1,7 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h) and of the
 // point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts and
-// group contacts; and of the half-sphere exposure, the lists within a cutoff and the k nearest atoms, which need the grid
-// alone.  The batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws;
+// group contacts; and of the half-sphere exposure, the lists within a cutoff, the k nearest atoms and the radial counts,
+// which need the grid alone.  The batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws;
 // nb_grid, and hs_grid for the runs on the grid alone), then neighbors.hip counts, scans and fills the lists (nb_count,
 // nb_fill).  A point run keeps the lists on the device: every family shares one prologue (pt_count, pt_prepare: lists
 // with the SASA path's cutoff, lattice, PtArgs) and adds its own kernels of points.hip, depth.hip or components.hip and
@@ -649,6 +649,54 @@ int nn_run(rsasa_context *ctx, const Cols &c, float probe, const uint8_t *flags,
     return RSASA_OK;
 }
 
+// One run of the radial counts: the grid alone and the flags as in hs_run, the class bytes and the structures' offsets
+// beside them, the dense table of rows ([N][n_classes][n_bins] uint32: held on the device even when only the pair
+// tables are asked for - k_radial_pairs sums its rows) and, when asked for, the pair tables, zeroed on the stream;
+// k_sort_kinds, k_radial_counts and k_radial_pairs; what was asked for comes back.  check_radial and check_classes have
+// passed.
+int rd_run(rsasa_context *ctx, const Cols &c, float probe, const uint8_t *flags, const uint8_t *classes, uint32_t n_classes,
+           const float *edges, uint32_t n_bins, uint32_t *out_counts, uint64_t *out_pairs)
+{
+    static_assert(kRadialMaxClasses == RSASA_RADIAL_MAX_CLASSES && kRadialMaxBins == RSASA_RADIAL_MAX_BINS,
+                  "the header's bounds are the kernels' bounds");
+    static_assert(sizeof(RdArgs::e2) == kRadialMaxBins * sizeof(float), "an edge per bin");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    const size_t N = c.N, cells = (size_t)n_classes * n_bins, pair_bytes = c.S * n_classes * cells * 8;
+    if (N == 0) {
+        if (out_pairs) std::memset(out_pairs, 0, pair_bytes);
+        return RSASA_OK;
+    }
+    int rc;
+    rsasa_context::RunScratch &R = ctx->run;
+    hipStream_t st = ctx->stream;
+    HsArgs h{};
+    RdArgs r{};
+    if ((rc = hs_grid(ctx, c, nullptr, probe, flags, h)) || (classes && (rc = reserve(ctx, R.classes, N))) ||
+        (rc = reserve(ctx, R.so, (c.S + 1) * 4)) || (rc = reserve(ctx, R.table, N * cells * 4)) ||
+        (out_pairs && (rc = reserve(ctx, R.pairs, pair_bytes))))
+        return rc;
+    if (classes) RS_HIP(ctx, hipMemcpyAsync(R.classes.p, classes, N, hipMemcpyHostToDevice, st));
+    RS_HIP(ctx, hipMemcpyAsync(R.so.p, c.so, (c.S + 1) * 4, hipMemcpyHostToDevice, st));
+    if (out_pairs) RS_HIP(ctx, hipMemsetAsync(R.pairs.p, 0, pair_bytes, st));
+    r.b = h.b;
+    r.flags = h.flags;
+    r.classes = classes ? (const uint8_t *)R.classes.p : nullptr;
+    r.sorted_kinds = h.sorted_flags;
+    r.so = (const uint32_t *)R.so.p;
+    r.n_classes = n_classes;
+    r.n_bins = n_bins;
+    for (uint32_t k = 0; k < n_bins; k++) r.e2[k] = edges[k] * edges[k];
+    r.table = (uint32_t *)R.table.p;
+    r.pairs = out_pairs ? (unsigned long long *)R.pairs.p : nullptr;
+    launch_radial(r, st);
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, download(out_counts, r.table, N * cells * 4, st));
+    RS_HIP(ctx, download(out_pairs, r.pairs, pair_bytes, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -873,6 +921,35 @@ int rsasa_nearest_atoms_batch(rsasa_context_t *ctx, const float *x, const float 
     RS_ARGS(ctx, check_nearest_cutoff(cutoff));
     return nn_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, flags, k, cutoff,
                   out_offsets, out_entries, entries_capacity);
+}
+
+int rsasa_radial_counts(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms, float probe_radius, const uint8_t *flags, const uint8_t *classes,
+                        uint32_t n_classes, const float *edges, uint32_t n_bins, uint32_t *out_counts, uint64_t *out_pairs)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    RS_ARGS(ctx, check_columns(n_atoms, x, y, z, radius, !n_atoms || out_counts || out_pairs));
+    RS_ARGS(ctx, check_radial(edges, n_bins, n_classes));
+    RS_ARGS(ctx, check_classes(classes, n_atoms, n_classes));
+    return rd_run(ctx, Cols(x, y, z, radius, id, n_atoms), probe_radius, flags, classes, n_classes, edges, n_bins, out_counts,
+                  out_pairs);
+}
+
+int rsasa_radial_counts_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                              const uint8_t *flags, const uint8_t *classes, uint32_t n_classes, const float *edges,
+                              uint32_t n_bins, uint32_t *out_counts, uint64_t *out_pairs)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    size_t N;
+    RS_ARGS(ctx, check_offsets(structure_offsets, n_structures, N));
+    RS_ARGS(ctx, check_columns(N, x, y, z, radius, !N || out_counts || out_pairs));
+    RS_ARGS(ctx, check_radial(edges, n_bins, n_classes));
+    RS_ARGS(ctx, check_classes(classes, N, n_classes));
+    return rd_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, flags, classes, n_classes,
+                  edges, n_bins, out_counts, out_pairs);
 }
 
 // No context, no device: double arithmetic in atom order on the host.

@@ -12,8 +12,8 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import (ATOM_DTYPE, NEAREST_MAX_K, NEIGHBOR_DTYPE, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch,
-                    RsasaError, Timings, check, ptr)
+from ._capi import (ATOM_DTYPE, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS, RADIAL_MAX_CLASSES, WITHIN_CENTRE,
+                    WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings, check, ptr)
 
 
 def device_count() -> int:
@@ -69,15 +69,16 @@ def _labels(groups, n):
     return np.ascontiguousarray(g, dtype=np.uint32)
 
 
-def _flag_bytes(flags, n):
-    """The flag bytes of half_sphere_exposure / atoms_within as a contiguous uint8 array of n entries, or None."""
+def _flag_bytes(flags, n, name="flags"):
+    """The flag bytes of half_sphere_exposure / atoms_within (or, under another name, the class bytes of radial_counts)
+    as a contiguous uint8 array of n entries, or None."""
     if flags is None:
         return None
     f = np.asarray(flags)
     if f.dtype.kind not in "ui" or f.shape != (n,):
-        raise ValueError(f"flags must be a 1-D array of {n} integer entries (uint8, one per atom)")
+        raise ValueError(f"{name} must be a 1-D array of {n} integer entries (uint8, one per atom)")
     if f.dtype != np.uint8 and f.size and (int(f.min()) < 0 or int(f.max()) > 0xFF):
-        raise ValueError("flags must lie in [0, 256)")
+        raise ValueError(f"{name} must lie in [0, 256)")
     return np.ascontiguousarray(f, dtype=np.uint8)
 
 
@@ -488,6 +489,51 @@ class Context:
         offsets over the whole batch, idx the index within the structure."""
         return self._nearest_atoms(x, y, z, radius, ids, probe_radius, k, flags, cutoff, structure_offsets)
 
+    # ---- radial counts (how many partners of which class in which distance bin; one sweep for every radius) ----
+    def _radial_counts(self, x, y, z, radius, ids, probe_radius, edges, classes, n_classes, flags, pairs,
+                       structure_offsets=_SINGLE):
+        (x, *_), entry = self._entry("radial_counts", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        flags = _flag_bytes(flags, n)
+        classes = _flag_bytes(classes, n, "classes")
+        if n_classes is None:
+            n_classes = 1 if classes is None or not classes.size else int(classes.max()) + 1
+        if isinstance(n_classes, (bool, float)) or int(n_classes) != n_classes or not 1 <= int(n_classes) <= RADIAL_MAX_CLASSES:
+            raise ValueError(f"n_classes must be an integer in [1, {RADIAL_MAX_CLASSES}]")
+        n_classes = int(n_classes)
+        edges = _f32(edges)
+        if edges.ndim != 1 or not 1 <= edges.shape[0] <= RADIAL_MAX_BINS:
+            raise ValueError(f"edges must be a 1-D array of 1 to {RADIAL_MAX_BINS} radii")
+        if pairs not in (False, True, "only"):
+            raise ValueError('pairs must be False, True or "only"')
+        n_bins = edges.shape[0]
+        n_struct = 1 if structure_offsets is _SINGLE else _offsets("structure_offsets", structure_offsets).shape[0] - 1
+        counts = None if pairs == "only" else np.zeros((n, n_classes, n_bins), np.uint32)
+        table = np.zeros((n_struct, n_classes, n_classes, n_bins), np.uint64) if pairs else None
+        self._check(entry(probe_radius, ptr(flags), ptr(classes), n_classes, ptr(edges), n_bins, ptr(counts), ptr(table)))
+        return table if pairs == "only" else (counts, table) if pairs else counts
+
+    def radial_counts(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, edges=(6.0, 8.0, 10.0, 12.0),
+                      classes=None, n_classes=None, flags=None, pairs=False):
+        """rsasa_radial_counts: counts uint32[N, C, B].  counts[i, b, k] is the number of atoms j != i with RADIAL_PARTNER
+        in flags[j] and classes[j] == b whose float32 d2 to i lies in bin k - the smallest k with d2 <= edges[k] *
+        edges[k], evaluated as the header defines it (plain float32, so the counts can be checked for equality) - for
+        every atom i with RADIAL_CENTRE in flags[i]; the other rows are zero.  edges: 1 to RADIAL_MAX_BINS radii, finite,
+        not negative, non-decreasing.  classes: a byte per atom below n_classes (None: everybody is class 0); n_classes
+        None: max(classes) + 1.  flags None: every atom is centre and partner.  pairs=True: (counts, table) with table
+        uint64[1, C, C, B], table[0, a, b, k] the sum of counts[i, b, k] over the centres i of class a (the pair-distance
+        histogram by class pair); pairs="only": the table alone, and no row crosses to the host.  np.cumsum(counts, -1)
+        .sum(1)[:, k] is the contact number at edges[k]; radial_density() divides by the shells' volumes.  radius and
+        probe_radius only fix the grid's cell size."""
+        return self._radial_counts(x, y, z, radius, ids, probe_radius, edges, classes, n_classes, flags, pairs)
+
+    def radial_counts_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
+                            edges=(6.0, 8.0, 10.0, 12.0), classes=None, n_classes=None, flags=None, pairs=False):
+        """rsasa_radial_counts_batch: radial_counts of every structure (one grid each, atoms of other structures never
+        count), rows in batch order; the pair tables are uint64[S, C, C, B], one per structure."""
+        return self._radial_counts(x, y, z, radius, ids, probe_radius, edges, classes, n_classes, flags, pairs,
+                                   structure_offsets)
+
     # ---- contact counts (which neighbour buries which points, reference src/lib.rs:129-146,183-207) ----
     def _contact_points(self, x, y, z, radius, ids, probe_radius, n_points, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -714,6 +760,25 @@ def residue_depth(depth, residue_offsets):
 
 HSE_PARTNER = 1  # flag bits of half_sphere_exposure: the atom is counted / the atom gets a result
 HSE_CENTRE = 2
+
+
+RADIAL_PARTNER = 1  # flag bits of radial_counts (those of half_sphere_exposure)
+RADIAL_CENTRE = 2
+
+
+def radial_density(counts, edges) -> np.ndarray:
+    """The counts of radial_counts[_batch] (any array whose last axis runs over the bins) as number densities, float64
+    of the same shape: every count divided by the volume of its shell, 4/3 pi (e_k^3 - e_(k-1)^3) with e_(-1) = 0.  An
+    empty shell (equal edges, or a first edge of 0) gives NaN.  Host arithmetic in float64."""
+    c = np.asarray(counts)
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim != 1 or c.ndim < 1 or c.shape[-1] != e.shape[0]:
+        raise ValueError("edges must be 1-D with one radius per bin of counts' last axis")
+    if e.size and (not np.isfinite(e).all() or e[0] < 0 or (np.diff(e) < 0).any()):
+        raise ValueError("edges must be finite, not negative and non-decreasing")
+    volume = 4.0 / 3.0 * np.pi * np.diff(e ** 3, prepend=0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(volume > 0.0, c.astype(np.float64) / volume, np.nan)
 
 
 def pseudo_cb_directions(ca_xyz, chain_offsets) -> np.ndarray:
