@@ -42,7 +42,8 @@ extern "C" {
  * rsasa_atom_depth, rsasa_atom_depth_batch; rsasa_surface_components, rsasa_surface_components_batch;
  * rsasa_half_sphere_exposure, rsasa_half_sphere_exposure_batch; rsasa_within_t, rsasa_atoms_within,
  * rsasa_atoms_within_batch; RSASA_NEAREST_MAX_K, rsasa_nearest_atoms, rsasa_nearest_atoms_batch;
- * RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS, rsasa_radial_counts, rsasa_radial_counts_batch. */
+ * RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS, rsasa_radial_counts, rsasa_radial_counts_batch;
+ * rsasa_contact_owners, rsasa_contact_owners_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -54,7 +55,7 @@ typedef enum rsasa_status {
     RSASA_ERR_GRID_TOO_LARGE = -5,   /* a structure's cell grid exceeds 2^31 cells (coordinates too sparse) */
     RSASA_ERR_INTERNAL = -6,
     RSASA_ERR_QUEUE_FULL = -7,       /* rsasa_host_batch_enqueue: eight batches are queued and not yet waited for */
-    RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*: out_entries is NULL or holds
+    RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*, rsasa_contact_owners*: out_entries is NULL or holds
                                         fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
                                         the same for its row buffers; rsasa_surface_components*: for out_labels;
                                         rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries */
@@ -1092,6 +1093,76 @@ int rsasa_contact_points_batch(rsasa_context_t *ctx,
                                uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
                                uint32_t *out_covered, uint32_t *out_exclusive, size_t entries_capacity,
                                float *out_atom_sasa);
+
+/* ---- contact owners ----------------------------------------------------- */
+
+/* A PARTITION of an atom's buried points among its neighbours: every point
+ * some entry of the list hits goes to exactly one entry, so the counts of an
+ * atom's entries add up to what the atom lost - the atom x atom (and, summed,
+ * residue x residue or chain x chain) table of buried area whose rows are
+ * additive.  out_covered counts a point once for every entry that hits it and
+ * out_exclusive drops every point two entries hit; out_owned lies between.
+ *
+ * Lists, hit(e, p), n_fused, out_sasa, sizing, argument errors, non-finite
+ * input, stream and workspace are all as rsasa_contact_points*.  For atom i,
+ * position e of its list (sorted by (d^2, idx)) and lattice point p, with
+ * (sx, sy, sz) the point, (vx, vy, vz) = centre_i - centre_idx and
+ * limit = (threshold_squared - d^2 - R*R) / (2*R) as the hit rule uses them,
+ * the margin is
+ *   m(e, p) = fmaf(sx, vx, fmaf(sy, vy, sz*vz)) - limit    for p < n_fused,
+ *   m(e, p) = ((sx*vx + sy*vy) + sz*vz) - limit            for later points:
+ * the same dot as the hit rule for that point, followed by one float32
+ * subtraction, unfused.  In exact arithmetic 2*R*m is |P - c_idx|^2 -
+ * threshold_squared with P = c_i + R*s: the power distance of the point to the
+ * neighbour's expanded sphere, negative where the entry hits.
+ *   owner(p) is found by walking the list in order: entry e takes the point if
+ *   hit(e, p) and either nobody owns it yet or m(e, p) < m(owner, p).
+ * Without NaN this is the hitting entry with the smallest (m, e): the buried
+ * part of the sphere is cut by the radical planes of the neighbours (the power
+ * diagram).  The earlier position wins an exact tie; -0 and +0 tie; a NaN limit
+ * never hits and so never owns; a free point has owner 0xFFFFFFFF.
+ *   out_owned[e] = #{p : owner(p) = e}, uint32, aligned with out_entries;
+ *                  entries that own nothing are kept.
+ * Hence, exactly, for every atom: the sum of out_owned over its entries is
+ * n_points - popcount(rsasa_accessible_points);
+ * out_exclusive[e] <= out_owned[e] <= out_covered[e]; and all three are equal
+ * for a list of one entry.  Counts are areas by the expression given for
+ * rsasa_contact_points.
+ *
+ * out_owner (nullable): uint32[n_atoms * n_points], row i in input order, the
+ * owner position of every point of atom i; the neighbour is
+ * out_entries[out_offsets[i] + owner].  It is the dot-level contact map:
+ * together with rsasa_sphere_points it colours every buried dot by partner.
+ * When it is NULL no device memory is reserved for it.  It is written only on
+ * RSASA_OK.
+ *
+ * Sizing: if out_entries or out_owned is NULL, or entries_capacity <
+ * out_offsets[n], out_offsets is written, nothing else, and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).
+ * out_offsets: [n_atoms + 1]; out_entries, out_owned: [entries_capacity];
+ * out_owner: [n_atoms * n_points] or NULL; out_sasa: [n_atoms] or NULL. */
+int rsasa_contact_owners(rsasa_context_t *ctx,
+                         const float *x, const float *y, const float *z, const float *radius,
+                         const uint64_t *id, size_t n_atoms,
+                         float probe_radius, size_t n_points,
+                         uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                         uint32_t *out_owned, size_t entries_capacity,
+                         uint32_t *out_owner, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each); out_offsets
+ * is batch-global [structure_offsets[n_structures] + 1], out_owner rows in
+ * batch order. */
+int rsasa_contact_owners_batch(rsasa_context_t *ctx,
+                               const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id,
+                               const uint32_t *structure_offsets, size_t n_structures,
+                               float probe_radius, size_t n_points,
+                               uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                               uint32_t *out_owned, size_t entries_capacity,
+                               uint32_t *out_owner, float *out_atom_sasa);
 
 /* ---- group contacts ----------------------------------------------------- */
 

@@ -150,6 +150,10 @@ SYMBOLS = {
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "rsasa_contact_points_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,
                                              C.c_size_t, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "rsasa_contact_owners": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
+                                       _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_contact_owners_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,
+                                             C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "rsasa_group_contacts": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                        _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, _vp]),
     "rsasa_group_contacts_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,

@@ -308,6 +308,16 @@ struct CtArgs {
     uint32_t *exclusive;                // [offsets[n_atoms]]: points of the atom the entry hits and no other entry of the list does
 };
 
+// ---- contact owners (points.hip, rsasa_contact_owners*) ----
+// The same lists and lattice (p.masks unused): every point some entry hits goes to ONE entry, the hitting entry with the
+// smallest margin dot - limit (the earlier position on a tie).
+struct CoArgs {
+    PtArgs p;                           // p.sasa: [n_atoms] or null, as CtArgs
+    uint32_t *owned;                    // [offsets[n_atoms]]: points of the atom the entry owns
+    uint32_t *owner;                    // [n_atoms][n_points] or null, input order: the owner's position in the atom's
+                                        // list, 0xFFFFFFFF for a point no entry hits
+};
+
 // ---- group contacts (points.hip, rsasa_group_contacts*) ----
 // The same lists and lattice (p.masks unused) and a label per atom: k_group_order reorders every list by label and counts
 // its rows (one per distinct foreign label), the host scans the counts into row_offsets, k_group_points fills the rows.
@@ -415,6 +425,7 @@ void launch_radial(const RdArgs &r, hipStream_t stream);
 void launch_neighbor_rank_spill(const NbArgs &a, uint64_t spill_atoms, hipStream_t stream);
 // The per-entry point counts (points.hip) from those lists.
 void launch_contact_points(const CtArgs &c, hipStream_t stream);
+void launch_contact_owners(const CoArgs &c, hipStream_t stream);
 // The 64-bit exclusive scan of the count pass by itself (neighbors.hip): a.counts -> a.offsets[0 .. n_atoms], totals -> a.info.
 void launch_neighbor_scan(const NbArgs &a, hipStream_t stream);
 // Group contacts (points.hip): the lists in label order and their row counts; then, with GpArgs::row_offsets, the rows.

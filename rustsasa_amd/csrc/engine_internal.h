@@ -445,7 +445,7 @@ struct rsasa_context {
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
     // rsasa_precompute_neighbors* and the point runs behind them - accessible points, exposure vectors, atom depth,
-    // surface components, contact counts, group contacts - and the half-sphere exposure (neighbors.cpp).  A workspace of their own: device batches in
+    // surface components, contact counts, contact owners, group contacts - and the half-sphere exposure (neighbors.cpp).  A workspace of their own: device batches in
     // flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls queue their work on `stream` behind whatever
     // it holds.  What outlives a call is here: the workspace's and the cell array's sizes, the pinned block the device's
     // verdicts come back in, and the lattice in the reference's order (the SASA path's cached lattices reorder the points
@@ -467,6 +467,7 @@ struct rsasa_context {
         DeviceBuffer vectors, keys;                                       // exposure sums; nearest-dot keys
         DeviceBuffer parent, labels;                                      // union-find forest and labels, per dot
         DeviceBuffer covered, exclusive;                                  // contact counts, per list entry
+        DeviceBuffer owned, owner;                                        // contact owners: per list entry; per point
         // group contacts: the labels, the lists in label order, own-group and row counts per atom, the rows
         DeviceBuffer group, sorted, sorted_group, own, nrows, groups, buried, only, self_free;
         // half-sphere exposure: the directions and flags, the flags in cell-sorted order, the two counts per atom

@@ -1,6 +1,6 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h) and of the
-// point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts and
-// group contacts; and of the half-sphere exposure, the lists within a cutoff, the k nearest atoms and the radial counts,
+// point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts, contact
+// owners and group contacts; and of the half-sphere exposure, the lists within a cutoff, the k nearest atoms and the radial counts,
 // which need the grid alone.  The batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws;
 // nb_grid, and hs_grid for the runs on the grid alone), then neighbors.hip counts, scans and fills the lists (nb_count,
 // nb_fill).  A point run keeps the lists on the device: every family shares one prologue (pt_count, pt_prepare: lists
@@ -436,6 +436,45 @@ int ct_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, uint
         RS_HIP(ctx, download(out_exclusive, ct.exclusive, total * 4, st));
     }
     RS_HIP(ctx, download(out_sasa, ct.p.sasa, c.N * 4, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+// ---- contact owners (rsasa_contact_owners*) ----
+
+// One run of the contact owners: the lists, sized and copied out as by ct_run, and k_contact_owners' count of every
+// entry beside them; the owner of every point too when the caller asks for it (no device memory for it otherwise).
+int co_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, uint64_t *out_offsets,
+           rsasa_neighbor_t *out_entries, uint32_t *out_owned, size_t cap, uint32_t *out_owner, float *out_sasa)
+{
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    if (c.N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    int rc;
+    rsasa_context::RunScratch &R = ctx->run;
+    Lists l;
+    CoArgs co{};
+    if ((rc = pt_count(ctx, c, probe, out_offsets, l))) return rc;
+    const size_t total = l.info.total;
+    if (!out_entries || !out_owned || cap < total)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "an entry buffer is NULL or holds fewer entries than out_offsets[n]");
+    if ((rc = pt_prepare(ctx, l, n_points, false, out_sasa != nullptr, co.p)) ||
+        (total && (rc = reserve(ctx, R.owned, total * 4))) || (out_owner && (rc = reserve(ctx, R.owner, c.N * n_points * 4))))
+        return rc;
+    co.owned = (uint32_t *)R.owned.p;  // (like the entries, not read when every list is empty)
+    co.owner = out_owner ? (uint32_t *)R.owner.p : nullptr;
+    hipStream_t st = ctx->stream;
+    launch_contact_owners(co, st);
+    RS_HIP(ctx, hipGetLastError());
+    if (total) {
+        RS_HIP(ctx, download(out_entries, co.p.entries, total * 8, st));
+        RS_HIP(ctx, download(out_owned, co.owned, total * 4, st));
+    }
+    RS_HIP(ctx, download(out_owner, co.owner, c.N * n_points * 4, st));
+    RS_HIP(ctx, download(out_sasa, co.p.sasa, c.N * 4, st));
     RS_HIP(ctx, hipStreamSynchronize(st));
     return RSASA_OK;
 }
@@ -1018,6 +1057,32 @@ int rsasa_contact_points_batch(rsasa_context_t *ctx, const float *x, const float
     RS_ARGS(ctx, check_points(N, x, y, z, radius, out_offsets, n_points));
     return ct_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, n_points, out_offsets,
                   out_entries, out_covered, out_exclusive, entries_capacity, out_atom_sasa);
+}
+
+int rsasa_contact_owners(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                         const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, uint64_t *out_offsets,
+                         rsasa_neighbor_t *out_entries, uint32_t *out_owned, size_t entries_capacity, uint32_t *out_owner,
+                         float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    RS_ARGS(ctx, check_points(n_atoms, x, y, z, radius, out_offsets, n_points));
+    return co_run(ctx, Cols(x, y, z, radius, id, n_atoms), probe_radius, n_points, out_offsets, out_entries, out_owned,
+                  entries_capacity, out_owner, out_sasa);
+}
+
+int rsasa_contact_owners_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                               const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures,
+                               float probe_radius, size_t n_points, uint64_t *out_offsets, rsasa_neighbor_t *out_entries,
+                               uint32_t *out_owned, size_t entries_capacity, uint32_t *out_owner, float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    size_t N;
+    RS_ARGS(ctx, check_offsets(structure_offsets, n_structures, N));
+    RS_ARGS(ctx, check_points(N, x, y, z, radius, out_offsets, n_points));
+    return co_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, n_points, out_offsets,
+                  out_entries, out_owned, entries_capacity, out_owner, out_atom_sasa);
 }
 
 int rsasa_group_contacts(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,

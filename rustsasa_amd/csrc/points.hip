@@ -9,6 +9,8 @@
 //                         two 32-bit words of the mask.
 //   k_contact_points      (rsasa_contact_points*) the same layout, no early exit: per entry of the list, the points it
 //                         hits (covered) and those it alone hits (exclusive), from two sweeps of the list per pass.
+//   k_contact_owners      (rsasa_contact_owners*) the same layout, one sweep per pass: every buried point goes to the
+//                         entry with the smallest margin dot - limit (owned per entry, the owner position per point).
 //   k_group_order         (rsasa_group_contacts*) one wave per atom: its list again with the entries of its own group
 //                         (label) first and the others by (label, position), each entry ranked by counting the keys
 //                         below its own; the number of distinct foreign labels is the atom's row count.
@@ -21,7 +23,7 @@
 //   k_mask_free           one thread per atom: the popcount of its mask (free[], input order), for the kernels that start
 //                         from the masks of a finished run (depth.hip, components.hip).
 //
-// The four point kernels share one frame, written once below: the atom and its list (pt_atom), the list staged in LDS
+// The five point kernels share one frame, written once below: the atom and its list (pt_atom), the list staged in LDS
 // (pt_stage: once by pt_stage_first when it fits one stage, else by pt_restage in every sweep, which holds the fences),
 // the lattice points of a pass (pt_load_points, pt_pass_begin), the two hit rules (pt_hit) and the value (pt_sasa).
 //
@@ -357,6 +359,110 @@ __global__ __launch_bounds__(256) void k_contact_points(CtArgs ct)
     if (lane == 0 && a.sasa) a.sasa[t.row] = pt_sasa(t.R2, exposed, a.n_points);
 }
 
+// ---- contact owners (rsasa_contact_owners*) ----
+
+constexpr uint32_t kCoFree = 0xFFFFFFFFu;  // the owner of a point no entry hits
+
+// Staged entries [0, n) (n a multiple of 4) - positions s0, s0 + 1, ... of the list - against the NCH chunks of a pass.
+// The margin of entry e at a point is the dot product its hit rule compares, minus the limit (one float32 subtraction,
+// not fused: -ffp-contract=off); a hitting entry takes the point when nobody owns it yet or its margin is below the
+// owner's, so of equal margins the earlier position keeps it.  The pad entries (limit -inf) and a NaN limit never hit;
+// `live` keeps the lanes past the last point (dot 0, which hits under a positive limit) from owning.
+template <int NCH, bool REM>
+__device__ __forceinline__ void co_test(const float4 *s_ent, uint32_t n, uint32_t s0, const PtPass<NCH> &ps,
+                                        float (&best_m)[NCH], uint32_t (&best_e)[NCH])
+{
+    for (uint32_t k = 0; k < n; k += 4) {
+        float4 e[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) e[u] = s_ent[k + u];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const uint32_t pos = s0 + k + u;  // (the same in every lane)
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                // pt_hit's two dots
+                float dot = __builtin_fmaf(ps.sx[c], e[u].x, __builtin_fmaf(ps.sy[c], e[u].y, ps.sz[c] * e[u].z));
+                bool hit = dot < e[u].w;
+                if (REM) {
+                    const float dotu = ps.sx[c] * e[u].x + ps.sy[c] * e[u].y + ps.sz[c] * e[u].z;
+                    hit = ps.rem[c] ? dotu <= e[u].w : hit;
+                    dot = ps.rem[c] ? dotu : dot;
+                }
+                const float m = dot - e[u].w;
+                const bool take = hit && ps.live[c] && (best_e[c] == kCoFree || m < best_m[c]);
+                best_m[c] = take ? m : best_m[c];
+                best_e[c] = take ? pos : best_e[c];
+            }
+        }
+    }
+}
+
+// The frame of k_contact_points, one sweep of the list per pass: every lane carries the smallest margin and its
+// position (best_m, best_e) of each of its points across the whole list, stages included.  After the sweep each lane
+// adds 1 to its owners' cells of s_cnt (LDS atomics), one window of kPtStage positions at a time, and the window is
+// added to owned[] as ct_sweep adds its counts across passes.  owner[] (nullable) gets every point's owner position.
+template <int NCH>
+__global__ __launch_bounds__(256) void k_contact_owners(CoArgs co)
+{
+    const PtArgs &a = co.p;
+    __shared__ float4 s_ent[4][kPtStage];
+    __shared__ uint32_t s_cnt[4][kPtStage];
+    const uint32_t w = threadIdx.x / kWave, lane = lane_id();
+    const uint32_t p = blockIdx.x * 4u + w;
+    if (p >= a.b.n_atoms) return;
+    const PtAtom t = pt_atom(a, a.entries, p);
+    const auto stage = [&](uint32_t s0, uint32_t n) __attribute__((always_inline)) { pt_stage(a, t, s0, n, s_ent[w]); };
+    pt_stage_first(t, stage);
+    uint32_t *owned = co.owned + t.off;
+    uint32_t *owner = co.owner ? co.owner + (size_t)t.row * a.n_points : nullptr;
+
+    // an empty list: no counts, no sweep, every point free
+    const uint32_t n_chunks = t.K ? (a.n_points + kWave - 1) / kWave : 0u;
+    if (!t.K && owner)
+        for (uint32_t pi = lane; pi < a.n_points; pi += kWave) owner[pi] = kCoFree;
+    float nx[NCH], ny[NCH], nz[NCH];
+    pt_load_points(a, 0u, n_chunks, nx, ny, nz);
+    uint32_t exposed = t.K ? 0u : a.n_points;
+    for (uint32_t c0 = 0; c0 < n_chunks; c0 += NCH) {
+        PtPass<NCH> ps;
+        float best_m[NCH];
+        uint32_t best_e[NCH];
+        const bool any_rem = pt_pass_begin(a, c0, n_chunks, nx, ny, nz, ps);
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            best_m[c] = __builtin_inff();
+            best_e[c] = kCoFree;
+        }
+        for (uint32_t s0 = 0; s0 < t.K; s0 += kPtStage) {
+            const uint32_t n4 = pt_pad4(pt_restage(t, s0, stage));
+            if (any_rem) co_test<NCH, true>(s_ent[w], n4, s0, ps, best_m, best_e);
+            else co_test<NCH, false>(s_ent[w], n4, s0, ps, best_m, best_e);
+        }
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            exposed += (uint32_t)__popcll(ballot64(ps.live[c] && best_e[c] == kCoFree));
+            const uint32_t pi = (c0 + c) * kWave + lane;
+            if (owner && pi < a.n_points) owner[pi] = best_e[c];  // coalesced
+        }
+        for (uint32_t s0 = 0; s0 < t.K; s0 += kPtStage) {
+            const uint32_t n = min(kPtStage, t.K - s0);
+            for (uint32_t e = lane; e < n; e += kWave) s_cnt[w][e] = 0u;
+            wave_lds_fence();
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const uint32_t rel = best_e[c] - s0;  // (a free point: kCoFree - s0 >= 2^32 - 2^31 > n)
+                if (rel < n) atomicAdd(&s_cnt[w][rel], 1u);
+            }
+            wave_lds_fence();
+            // lane l owns entries l, l + 64, ... in every pass, so what it adds to is its own earlier write
+            for (uint32_t e = lane; e < n; e += kWave) owned[s0 + e] = s_cnt[w][e] + (c0 != 0 ? owned[s0 + e] : 0u);
+            wave_lds_fence();  // (every lane has read the counts before the next window clears them)
+        }
+    }
+    if (lane == 0 && a.sasa) a.sasa[t.row] = pt_sasa(t.R2, exposed, a.n_points);
+}
+
 // ---- group contacts (rsasa_group_contacts*) ----
 
 // The sort key of entry e (its position in the list, below 2^31) with label `lab` in the list of an atom labelled `mine`:
@@ -665,6 +771,12 @@ void launch_mask_free(const PtArgs &a, uint32_t *free, hipStream_t stream)
 void launch_contact_points(const CtArgs &c, hipStream_t stream)
 {
     pt_launch(k_contact_points<2>, k_contact_points<4>, c.p, c, stream);
+}
+
+// owned[] (and owner[] and p.sasa[], if set) of every atom of the binned batch
+void launch_contact_owners(const CoArgs &c, hipStream_t stream)
+{
+    pt_launch(k_contact_owners<2>, k_contact_owners<4>, c.p, c, stream);
 }
 
 // sorted[], sorted_group[], n_own[] and n_rows[] of every atom of the binned batch

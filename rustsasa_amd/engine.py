@@ -558,6 +558,37 @@ class Context:
         idx the index within the structure."""
         return self._contact_points(x, y, z, radius, ids, probe_radius, n_points, structure_offsets)
 
+    # ---- contact owners (every buried point given to one neighbour: an additive split of the buried points) ----
+    def _contact_owners(self, x, y, z, radius, ids, probe_radius, n_points, points, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("contact_owners", x, y, z, radius, ids, structure_offsets)
+        sasa = np.zeros(x.shape[0], np.float32)
+        owner = np.full((x.shape[0], n_points), 0xFFFFFFFF, np.uint32) if points else None
+
+        def call(offsets, entries, owned, cap):
+            return entry(probe_radius, n_points, ptr(offsets), ptr(entries), ptr(owned), cap, ptr(owner), ptr(sasa))
+        out = self._sized_call(call, x.shape[0], 64 * x.shape[0], NEIGHBOR_DTYPE, np.uint32) + (sasa,)
+        return out + (owner,) if points else out
+
+    def contact_owners(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100,
+                       points: bool = False):
+        """rsasa_contact_owners: (offsets uint64[N + 1], entries NEIGHBOR_DTYPE[total], owned uint32[total],
+        sasa float32[N]), and with points=True also owner uint32[N, n_points].  offsets / entries / sasa are those of
+        contact_points.  Every point of sphere_points(n_points) on atom i that some entry of its list occludes belongs
+        to ONE entry, the hitting entry with the smallest margin dot - limit in float32 (the power distance of the point
+        to the neighbour's expanded sphere; the earlier list position on an exact tie): owned[e] counts the points entry
+        e owns, so the owned counts of an atom add up to n_points minus its accessible points, and
+        exclusive <= owned <= covered entry by entry.  owner[i, p] is the owner's position in atom i's list - the
+        neighbour is entries[offsets[i] + owner[i, p]] - or 0xFFFFFFFF for an accessible point.  contact_areas() turns
+        owned into A^2; owner_areas() sums it into an additive group x group table."""
+        return self._contact_owners(x, y, z, radius, ids, probe_radius, n_points, points)
+
+    def contact_owners_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4,
+                             n_points: int = 100, points: bool = False):
+        """rsasa_contact_owners_batch: contact_owners of every structure (one grid each); offsets over the whole batch,
+        idx the index within the structure, owner rows in batch order."""
+        return self._contact_owners(x, y, z, radius, ids, probe_radius, n_points, points, structure_offsets)
+
     # ---- group contacts (which partner group buries which points: unions of the same tests over a label's entries) ----
     def _group_contacts(self, x, y, z, radius, ids, groups, probe_radius, n_points, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -817,13 +848,18 @@ def _within_pairs(offsets, entries, structure_offsets):
         raise ValueError("entries must be a WITHIN_DTYPE array of offsets[-1] entries")
     n = off.shape[0] - 1
     centre = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
+    return centre, _structure_base(n, structure_offsets)[centre] + ent["idx"].astype(np.int64)
+
+
+def _structure_base(n, structure_offsets):
+    """int64[n]: the first atom of every atom's structure (zeros for structure_offsets None: one structure)."""
     base = np.zeros(n, np.int64)
     if structure_offsets is not None:
         so = np.asarray(structure_offsets).astype(np.int64)
         if so.ndim != 1 or so.shape[0] < 1 or so[0] != 0 or so[-1] != n or (np.diff(so) < 0).any():
             raise ValueError("structure_offsets must be non-decreasing from 0 to the number of atoms")
         base = so[np.searchsorted(so[1:], np.arange(n), side="right")] if n else base
-    return centre, base[centre] + ent["idx"].astype(np.int64)
+    return base
 
 
 def edge_index(offsets, entries, structure_offsets=None) -> np.ndarray:
@@ -1024,6 +1060,34 @@ def group_areas(offsets, partner_groups, counts, groups, radius, probe_radius: f
     return (pairs >> np.uint64(32)).astype(np.uint32), (pairs & np.uint64(0xFFFFFFFF)).astype(np.uint32), total
 
 
+def owner_areas(offsets, entries, owned, labels, radius, probe_radius: float = 1.4, n_points: int = 100,
+                structure_offsets=None):
+    """The owned counts of contact_owners[_batch] summed into a label x label table: (from_label uint32[P],
+    to_label uint32[P], area float64[P]), one entry per distinct ordered pair (label of the atom, label of the entry's
+    neighbour) that has an entry, sorted by (from, to).  area is the area of the atoms labelled `from` that the atoms
+    labelled `to` own: every entry's area by contact_areas' float32 expression (R of the atom whose list holds the
+    entry), summed in float64.  from == to is included: the area lost inside a group.  labels: one integer label per
+    atom, over the whole batch; structure_offsets (the batch form's) makes idx batch-global, None: one structure.
+    The table is ADDITIVE: for every label A, the sum over B of area(A, B) plus A's SASA is the sum of 4 pi R^2 over
+    A's atoms (up to the float32 rounding of each term), and in counts this holds exactly - the owned counts of
+    A's atoms plus their accessible points are n_points per atom."""
+    area = contact_areas(owned, offsets, radius, probe_radius, n_points)
+    off = np.ascontiguousarray(offsets, dtype=np.uint64).astype(np.int64)
+    n = off.shape[0] - 1
+    labels = _labels(labels, n)
+    ent = np.asarray(entries)
+    if ent.dtype != NEIGHBOR_DTYPE or ent.ndim != 1 or ent.shape[0] != area.shape[0]:
+        raise ValueError("entries must be a NEIGHBOR_DTYPE array of offsets[-1] entries")
+    centre = np.repeat(np.arange(n, dtype=np.int64), np.diff(off))
+    partner = _structure_base(n, structure_offsets)[centre] + ent["idx"].astype(np.int64)
+    if partner.size and int(partner.max()) >= n:
+        raise ValueError("an entry's idx lies outside its structure: are the structure_offsets those of the call?")
+    key = (labels[centre].astype(np.uint64) << np.uint64(32)) | labels[partner].astype(np.uint64)
+    pairs, inverse = np.unique(key, return_inverse=True)
+    total = np.bincount(inverse.reshape(-1), weights=area.astype(np.float64), minlength=pairs.shape[0])
+    return (pairs >> np.uint64(32)).astype(np.uint32), (pairs & np.uint64(0xFFFFFFFF)).astype(np.uint32), total
+
+
 def make_atoms(x, y, z, radius, ids) -> np.ndarray:
     """Packs SoA columns into rsasa_atom_t records."""
     a = np.zeros(len(x), ATOM_DTYPE)
@@ -1036,5 +1100,5 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 
 
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
-           "contact_areas", "group_areas", "sas_volume", "residue_depth", "default_link", "component_table", "split_sasa",
+           "contact_areas", "group_areas", "owner_areas", "sas_volume", "residue_depth", "default_link", "component_table", "split_sasa",
            "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
