@@ -1,8 +1,11 @@
-"""The ten families that share one host prologue and one set of scratch buffers (neighbors.cpp: neighbour lists,
-accessible points, exposure vectors, atom depth, surface components, contact counts, group contacts, half-sphere
-exposure, atoms within a cutoff, nearest atoms - the last three add the flags, directions, counts and rows to the scratch
-and keep the centres' ranks in the neighbour runs' map), walked in an order that makes every shared buffer grow, be
-reused while oversized, and serve another family than the one that sized it.
+"""The twelve families that share one host prologue and one set of scratch buffers (neighbors.cpp: neighbour lists,
+accessible points, exposure vectors, atom depth, surface components, contact counts, contact owners, group contacts,
+radial counts, half-sphere exposure, atoms within a cutoff, nearest atoms - the last three add the flags, directions,
+counts and rows to the scratch and keep the centres' ranks in the neighbour runs' map; the radial counts write
+(class << 2) | flags into the sorted-flags buffer those three read as plain flags, and stand before them in the walk, so
+the forward walk runs radial -> hse / within / nearest with flags NULL over class bits and the reverse walk the other
+way), walked in an order that makes every shared buffer grow, be reused while oversized, and serve another family than
+the one that sized it.
 What the per-family suites cannot see: a first call on a fresh context whose every list is empty (no fill has ever run,
 the entries' buffer does not exist yet), and a result that depends on which family ran before.
 
@@ -22,15 +25,20 @@ import hse_cases as hc
 import hse_model as hm
 import nb_helpers as nh
 import nearest_model as nm
+import owners_model as om
 import points_model as pm
+import radial_cases as rc
+import radial_model as rm
 import within_model as wm
 
 pytestmark = pytest.mark.gpu
 
 PROBE = 1.4
 N_POINTS = (100, 129)  # 4 mask words, 4 points past the fused 96; 5 words, the last holding the one point past the fused 128
-ORDER = ("points", "groups", "depth", "contacts", "components", "exposure", "neighbours", "hse", "within", "nearest")
-CUTOFF_TRIO = ("hse", "within", "nearest")   # n_points is ignored
+ORDER = ("points", "groups", "depth", "contacts", "owners", "components", "exposure", "neighbours", "radial", "hse", "within",
+         "nearest")
+CUTOFF_TRIO = ("hse", "within", "nearest")   # n_points is ignored (by "radial" too)
+RADIAL_CLASSES = 16
 HSE_CUTOFF, WITHIN_CUTOFF, NEAREST_K = 13.0, 8.0, 16
 
 
@@ -57,6 +65,11 @@ def _dirs(n):
     return hc.random_dirs(n, 83)
 
 
+@functools.lru_cache(maxsize=None)
+def _classes(n):
+    return rc.classes_of(n, RADIAL_CLASSES, 84)
+
+
 def _call(ctx, family, inp, n_points):
     """The family's call on `inp` (the single-structure method, or the batch method when the input has offsets) as a
     tuple of arrays."""
@@ -74,6 +87,12 @@ def _call(ctx, family, inp, n_points):
     if family == "nearest":
         tail = (PROBE, NEAREST_K)
         return ctx.nearest_atoms_batch(*cols, so, *tail) if batch else ctx.nearest_atoms(*cols, *tail)
+    if family == "radial":
+        tail = (PROBE, rc.EDGES, _classes(len(x)), RADIAL_CLASSES, None, True)
+        return ctx.radial_counts_batch(*cols, so, *tail) if batch else ctx.radial_counts(*cols, *tail)
+    if family == "owners":
+        tail = (PROBE, n_points, True)
+        return ctx.contact_owners_batch(*cols, so, *tail) if batch else ctx.contact_owners(*cols, *tail)
     if family == "groups":
         tail = (PROBE, n_points)
         return ctx.group_contacts_batch(*cols, groups, so, *tail) if batch else ctx.group_contacts(*cols, groups, *tail)
@@ -126,6 +145,17 @@ def test_first_call_on_a_fresh_context_has_only_empty_lists(alone, family):
     if family in ("within", "nearest"):
         offsets, entries = got
         assert np.array_equal(offsets, none) and entries.shape == (0,) and entries.dtype == wm.WITHIN_DTYPE
+        return
+    if family == "radial":
+        table, pairs = got
+        assert table.dtype == np.uint32 and table.shape == (1, RADIAL_CLASSES, len(rc.EDGES)) and not table.any()
+        assert pairs.dtype == np.uint64 and pairs.shape == (1, RADIAL_CLASSES, RADIAL_CLASSES, len(rc.EDGES)) and not pairs.any()
+        return
+    if family == "owners":
+        offsets, entries, owned, value, owner = got
+        assert np.array_equal(offsets, none) and entries.shape == owned.shape == (0,) and owned.dtype == np.uint32
+        assert owner.dtype == np.uint32 and owner.shape == (1, n_points) and np.all(owner == om.FREE)     # 0xFFFFFFFF
+        assert value.tobytes() == sasa.tobytes()                        # every point free: the full sphere
         return
     assert got[-1].tobytes() == sasa.tobytes()
     if family == "points":
@@ -189,3 +219,13 @@ def test_fixture_equals_the_models(alone, n_points):
     assert _same(alone[("within", "B", n_points)], within)
     assert _same(alone[("nearest", "B", n_points)], nm.truncate(*wm.lists(x, y, z, None, float("inf")), NEAREST_K))
     assert wm.lengths(within[0]).max() > NEAREST_K
+    offsets, entries, owned, value, owner = alone[("owners", "B", n_points)]
+    want = om.owners(x, y, z, r, ids, PROBE, n_points, 8)
+    nh.assert_same((offsets, entries), want[:2])
+    assert np.array_equal(owned, want[2]) and np.array_equal(owner, want[3]) and owned.any()
+    assert np.array_equal((owner == om.FREE).sum(axis=1).astype(np.uint32), free_want)
+    assert value.tobytes() == pm.sasa_of(r, PROBE, free_want, n_points).tobytes()
+    table, pairs = alone[("radial", "B", n_points)]
+    want = rm.counts(x, y, z, rc.EDGES, _classes(len(x)), RADIAL_CLASSES, None)
+    assert table.dtype == want.dtype and np.array_equal(table, want) and table.any(axis=(0, 2)).all()
+    assert np.array_equal(pairs, rm.pairs_from_counts(want, [0, len(x)], _classes(len(x))))
