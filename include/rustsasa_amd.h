@@ -43,7 +43,8 @@ extern "C" {
  * rsasa_half_sphere_exposure, rsasa_half_sphere_exposure_batch; rsasa_within_t, rsasa_atoms_within,
  * rsasa_atoms_within_batch; RSASA_NEAREST_MAX_K, rsasa_nearest_atoms, rsasa_nearest_atoms_batch;
  * RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS, rsasa_radial_counts, rsasa_radial_counts_batch;
- * rsasa_contact_owners, rsasa_contact_owners_batch. */
+ * rsasa_contact_owners, rsasa_contact_owners_batch; RSASA_CROWD_MAX_BINS, rsasa_dot_crowding,
+ * rsasa_dot_crowding_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -58,6 +59,7 @@ typedef enum rsasa_status {
     RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*, rsasa_contact_owners*: out_entries is NULL or holds
                                         fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
                                         the same for its row buffers; rsasa_surface_components*: for out_labels;
+                                        rsasa_dot_crowding*: for out_counts;
                                         rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries */
 } rsasa_status;
 
@@ -674,6 +676,103 @@ int rsasa_surface_components_batch(rsasa_context_t *ctx,
                                    uint64_t *out_dot_offsets,
                                    uint32_t *out_labels, size_t labels_capacity,
                                    uint32_t *out_free, float *out_atom_sasa);
+
+/* ---- dot crowding ------------------------------------------------------- */
+
+/* HOW MUCH PROTEIN lies around each point of the accessible surface: per
+ * accessible dot the number of partner atoms of its structure by distance bin -
+ * the buriedness of a surface point that pocket finders and surface
+ * fingerprints start from.  A dot in a groove or a pocket has many atoms within
+ * 8 - 10 A, a dot on a knob has few, and one atom often owns both kinds: the
+ * result is per dot, where rsasa_radial_counts is per atom.
+ *
+ * Definition.  Take one structure, probe p, lattice
+ * s = rsasa_sphere_points(n_points); A_i is the mask of rsasa_accessible_points
+ * under the context's current lane count.  Dots, their order and their
+ * numbering are exactly those of rsasa_surface_components: the dots are the
+ * pairs (i, k) with k in A_i, ordered by (i, k); out_dot_offsets is the
+ * exclusive scan of the free counts, batch-global in the batch form.  Each atom
+ * j has a flag byte f_j: bit 0 (RSASA_CROWD_PARTNER) - the atom is a partner, it
+ * is counted; the other bits are ignored.  edges[0 .. n_bins) are the bins'
+ * outer radii.  All arithmetic is float32, unfused, left to right:
+ *
+ *     R_i   = r_i + p
+ *     q     = (c_i.x + R_i * s_k.x, c_i.y + R_i * s_k.y, c_i.z + R_i * s_k.z)     the dot (i, k)
+ *     e2[b] = edges[b] * edges[b]        (may overflow to +inf, underflow to 0)
+ *     dx = c_j.x - q.x                   (dy, dz alike)
+ *     d2 = dx * dx + dy * dy + dz * dz
+ *     j counts for the dot  iff  j is in the SAME structure, (f_j & 1),
+ *                                d2 <= e2[n_bins - 1]
+ *     bin = the smallest b with d2 <= e2[b]
+ *     out_counts[dot][bin] += 1
+ *
+ * The dot's own atom i is an atom like any other: it counts if its partner bit
+ * is set, in the bin where d2 (about R_i^2) falls.  flags == NULL: every atom is
+ * a partner.  A NaN d2 counts nowhere - the dots of an atom with a NaN
+ * coordinate or radius get all-zero rows, and such an atom counts for nobody.
+ * Of several equal edges the first takes the pair and the others stay empty, as
+ * in rsasa_radial_counts.  Atom ids play no part beyond the masks.  The counts
+ * are integers and have no order, so they can be checked for equality.
+ * Unlike the calls on the grid alone, radius and probe_radius matter here: they
+ * place the dots.
+ *
+ *   out_dot_offsets  [n + 1], as rsasa_surface_components writes it;
+ *   out_counts       [counts_capacity][n_bins], row-major: row d is dot d, the
+ *                    rows line up one to one with out_labels of
+ *                    rsasa_surface_components;
+ *   out_free[i]      (nullable) the exposed count: the popcount of
+ *                    rsasa_accessible_points;
+ *   out_sasa[i]      (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Sizing, as rsasa_surface_components: out_dot_offsets is always written (on
+ * success and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_counts is NULL or
+ * counts_capacity (in dots) < out_dot_offsets[n], nothing else is written and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned: call once to size, allocate, call
+ * again.  A batch with 2^32 or more dots returns RSASA_ERR_INVALID_ARGUMENT.
+ *
+ * n_bins must lie in [1, RSASA_CROWD_MAX_BINS]; every edge must be finite and
+ * >= 0 (-0.0 is 0) and the edges non-decreasing (equal edges are allowed);
+ * anything else, and NULL edges, returns RSASA_ERR_INVALID_ARGUMENT.  The
+ * remaining argument errors and the non-finite input rules are those of
+ * rsasa_atom_depth: a NaN coordinate or radius is taken, an infinite coordinate
+ * returns RSASA_ERR_GRID_TOO_LARGE and the context stays usable.  No atoms:
+ * RSASA_OK with out_dot_offsets[0] = 0.  The call holds 4 * n_bins bytes per dot
+ * on the device; a failed reservation returns RSASA_ERR_OUT_OF_MEMORY and the
+ * context stays usable.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  The
+ * masks and lists stay on the device; 8 bytes per atom and 4 * n_bins per dot
+ * cross the link (and 4 per atom each for out_free and out_sasa). */
+#define RSASA_CROWD_PARTNER 1
+#define RSASA_CROWD_MAX_BINS 8
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).  flags:
+ * [n_atoms] or NULL; edges: [n_bins]; out_dot_offsets: [n_atoms + 1];
+ * out_counts: [counts_capacity][n_bins]; out_free, out_sasa: [n_atoms] or NULL. */
+int rsasa_dot_crowding(rsasa_context_t *ctx,
+                       const float *x, const float *y, const float *z, const float *radius,
+                       const uint64_t *id, size_t n_atoms,
+                       float probe_radius, size_t n_points,
+                       const uint8_t *flags, const float *edges, uint32_t n_bins,
+                       uint64_t *out_dot_offsets,
+                       uint32_t *out_counts, size_t counts_capacity,
+                       uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid and one max radius each; an empty
+ * structure is legal); atoms of other structures never count.  flags runs over
+ * structure_offsets[n_structures] atoms; out_dot_offsets is batch-global
+ * [structure_offsets[n_structures] + 1]. */
+int rsasa_dot_crowding_batch(rsasa_context_t *ctx,
+                             const float *x, const float *y, const float *z, const float *radius,
+                             const uint64_t *id,
+                             const uint32_t *structure_offsets, size_t n_structures,
+                             float probe_radius, size_t n_points,
+                             const uint8_t *flags, const float *edges, uint32_t n_bins,
+                             uint64_t *out_dot_offsets,
+                             uint32_t *out_counts, size_t counts_capacity,
+                             uint32_t *out_free, float *out_atom_sasa);
 
 /* ---- half-sphere exposure ----------------------------------------------- */
 

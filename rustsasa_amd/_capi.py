@@ -41,6 +41,7 @@ WITHIN_CENTRE = 2
 NEAREST_MAX_K = 256  # RSASA_NEAREST_MAX_K: the largest k of rsasa_nearest_atoms*
 RADIAL_MAX_CLASSES = 16  # RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS: the widest row of rsasa_radial_counts*
 RADIAL_MAX_BINS = 32
+CROWD_MAX_BINS = 8  # RSASA_CROWD_MAX_BINS: the widest row of rsasa_dot_crowding*
 
 
 class RsasaError(RuntimeError):
@@ -130,6 +131,10 @@ SYMBOLS = {
                                            _vp, _vp, C.c_size_t, _vp, _vp]),
     "rsasa_surface_components_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float,
                                                  C.c_size_t, C.c_float, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_dot_crowding": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, _vp, _vp, C.c_uint32,
+                                     _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_dot_crowding_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, _vp, _vp,
+                                           C.c_uint32, _vp, _vp, C.c_size_t, _vp, _vp]),
     "rsasa_half_sphere_exposure": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp, C.c_float,
                                              _vp, _vp]),
     "rsasa_half_sphere_exposure_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, _vp,

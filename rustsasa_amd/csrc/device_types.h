@@ -249,6 +249,20 @@ struct CcArgs {
     float link, link2;                  // two dots are linked when d2 <= link2 = link * link (one float32 product)
 };
 
+// ---- dot crowding (crowding.hip, rsasa_dot_crowding*) ----
+// A finished point run (p.masks written, in input order), the grid it ran on and a flag byte per atom: the accessible
+// dots numbered as CcArgs numbers them and, per dot, the partner atoms of its structure by distance bin.
+struct DcArgs {
+    PtArgs p;                           // p.masks, p.words: the masks k_accessible_points wrote; p.sasa as there
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_mask_free)
+    const unsigned long long *dot_offsets;  // [n_atoms + 1] exclusive scan of free: atom i's rows are [dot_offsets[i], dot_offsets[i + 1])
+    const uint8_t *sorted_flags;        // [n_atoms] HsArgs::sorted_flags (k_sort_flags): bit 0 - the atom is a partner
+    uint32_t n_bins;                    // 1 .. kCrowdMaxBins (entry_checks.h)
+    float e2[8];                        // the squared edges, edges[k] * edges[k] (one float32 product), non-decreasing;
+                                        // [n_bins .. 8) repeat the last one
+    uint32_t *counts;                   // [dot_offsets[n_atoms]][n_bins]: every row is written
+};
+
 // ---- half-sphere exposure (hse.hip, rsasa_half_sphere_exposure*) ----
 // A binned batch (no neighbour lists) with a direction and a flag byte per atom: per centre the partners of its own
 // structure within the cutoff, split by the side of the plane through the centre that is normal to its direction.
@@ -403,6 +417,8 @@ void launch_mask_free(const PtArgs &a, uint32_t *free, hipStream_t stream);
 void launch_atom_depth(const DpArgs &d, hipStream_t stream);
 // The component labels of the dots (components.hip) from those masks and counts, with CcArgs::dot_offsets.
 void launch_components(const CcArgs &c, hipStream_t stream);
+// The rows of the dots (crowding.hip) from those masks and counts, with DcArgs::dot_offsets and ::sorted_flags.
+void launch_dot_crowding(const DcArgs &d, hipStream_t stream);
 // The half-sphere counts (hse.hip) on a binned batch: the flags in cell-sorted order, then up[] and down[].
 void launch_half_sphere(const HsArgs &h, hipStream_t stream);
 // The keys k_neighbor_fill / k_within_fill stage per list in LDS: what NbArgs::stage is set to for their runs.

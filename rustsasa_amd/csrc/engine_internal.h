@@ -475,6 +475,7 @@ struct rsasa_context {
         DeviceBuffer rows;  // the k nearest atoms: a row of k keys per centre (NnArgs::rows)
         // radial counts: the class bytes, the structures' offsets, the dense table of rows, the pair tables (RdArgs)
         DeviceBuffer classes, so, table, pairs;
+        DeviceBuffer crowd;  // dot crowding: a row of n_bins counts per dot (DcArgs::counts)
     } run;
 };
 

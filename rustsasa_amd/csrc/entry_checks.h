@@ -89,16 +89,30 @@ inline const char *check_nearest_k(uint32_t k)
 // 0), non-decreasing (equal edges are allowed), and 1 .. RSASA_RADIAL_MAX_CLASSES classes - a row of k_radial_counts'
 // histogram is n_classes * n_bins cells of LDS.
 constexpr uint32_t kRadialMaxClasses = 16, kRadialMaxBins = 32;
-inline const char *check_radial(const float *edges, uint32_t n_bins, uint32_t n_classes)
+// The edges themselves, n_bins of them (the caller has bounded n_bins): what check_radial and check_crowding share.
+inline const char *check_edges(const float *edges, uint32_t n_bins)
 {
-    if (n_classes < 1u || n_classes > kRadialMaxClasses) return "n_classes must be in [1, 16]";
-    if (n_bins < 1u || n_bins > kRadialMaxBins) return "n_bins must be in [1, 32]";
     if (!edges) return "NULL argument";
     for (uint32_t k = 0; k < n_bins; k++) {
         if (!(edges[k] >= 0.0f) || std::isinf(edges[k])) return "edges must be finite and not negative";
         if (k && edges[k] < edges[k - 1u]) return "edges must be non-decreasing";
     }
     return nullptr;
+}
+inline const char *check_radial(const float *edges, uint32_t n_bins, uint32_t n_classes)
+{
+    if (n_classes < 1u || n_classes > kRadialMaxClasses) return "n_classes must be in [1, 16]";
+    if (n_bins < 1u || n_bins > kRadialMaxBins) return "n_bins must be in [1, 32]";
+    return check_edges(edges, n_bins);
+}
+
+// The bins of the dot crowding: 1 .. RSASA_CROWD_MAX_BINS edges under the rules of check_radial's - a dot's counters
+// are registers of k_dot_crowding.
+constexpr uint32_t kCrowdMaxBins = 8;
+inline const char *check_crowding(const float *edges, uint32_t n_bins)
+{
+    if (n_bins < 1u || n_bins > kCrowdMaxBins) return "n_bins must be in [1, 8]";
+    return check_edges(edges, n_bins);
 }
 
 // The class bytes of N atoms (nullable: every atom is class 0): every one below n_classes, on any atom.

@@ -1,6 +1,6 @@
 // Host side of the neighbour-list entry points (rsasa_precompute_neighbors / _batch, include/rustsasa_amd.h) and of the
-// point runs built on them: accessible points, exposure vectors, atom depth, surface components, contact counts, contact
-// owners and group contacts; and of the half-sphere exposure, the lists within a cutoff, the k nearest atoms and the radial counts,
+// point runs built on them: accessible points, exposure vectors, atom depth, surface components, dot crowding, contact
+// counts, contact owners and group contacts; and of the half-sphere exposure, the lists within a cutoff, the k nearest atoms and the radial counts,
 // which need the grid alone.  The batch's grid is built by the SASA path's kernels in a workspace of the context's own (rsasa_context::nb_ws;
 // nb_grid, and hs_grid for the runs on the grid alone), then neighbors.hip counts, scans and fills the lists (nb_count,
 // nb_fill).  A point run keeps the lists on the device: every family shares one prologue (pt_count, pt_prepare: lists
@@ -397,6 +397,73 @@ int cc_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, floa
     }
     RS_HIP(ctx, download(out_free, cc.free, c.N * 4, st));
     RS_HIP(ctx, download(out_sasa, cc.p.sasa, c.N * 4, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    return RSASA_OK;
+}
+
+// ---- dot crowding (rsasa_dot_crowding*) ----
+
+// One run of the dot crowding: cc_run's front half - the masks stay on the device, k_mask_free counts them, the scan of
+// the neighbour counts turns the counts into out_offsets, the caller's buffer is checked against out_offsets[N] - with
+// the flag bytes uploaded beside it (flags: host, [N], nullable) and sorted by k_sort_flags; then k_dot_crowding fills a
+// row of n_bins counts per dot.  8 bytes per atom and 4 * n_bins per dot come back (and 4 per atom each for the counts
+// and the values, if asked).  check_crowding has passed.
+int dc_run(rsasa_context *ctx, const Cols &c, float probe, size_t n_points, const uint8_t *flags, const float *edges,
+           uint32_t n_bins, uint64_t *out_offsets, uint32_t *out_counts, size_t cap, uint32_t *out_free, float *out_sasa)
+{
+    static_assert(kCrowdMaxBins == RSASA_CROWD_MAX_BINS, "the header's bound is the kernel's bound");
+    static_assert(sizeof(DcArgs::e2) == kCrowdMaxBins * sizeof(float), "an edge per bin");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    RS_DEVICE(ctx);
+    if (c.N == 0) {
+        out_offsets[0] = 0;
+        return RSASA_OK;
+    }
+    int rc;
+    rsasa_context::RunScratch &R = ctx->run;
+    Lists l;
+    DcArgs dc{};
+    if ((rc = pt_count(ctx, c, probe, nullptr, l)) || (rc = pt_prepare(ctx, l, n_points, true, out_sasa != nullptr, dc.p)) ||
+        (rc = reserve(ctx, R.free, c.N * 4)) || (rc = reserve(ctx, R.row_offsets, (c.N + 1) * 8)) ||
+        (flags && (rc = reserve(ctx, R.flags, c.N))) || (rc = reserve(ctx, R.sorted_flags, c.N)))
+        return rc;
+    hipStream_t st = ctx->stream;
+    if (flags) RS_HIP(ctx, hipMemcpyAsync(R.flags.p, flags, c.N, hipMemcpyHostToDevice, st));
+    HsArgs h{};
+    h.b = dc.p.b;
+    h.flags = flags ? (const uint8_t *)R.flags.p : nullptr;
+    h.sorted_flags = (uint8_t *)R.sorted_flags.p;
+    dc.free = (uint32_t *)R.free.p;
+    dc.dot_offsets = (const unsigned long long *)R.row_offsets.p;
+    dc.sorted_flags = h.sorted_flags;
+    dc.n_bins = n_bins;
+    for (uint32_t k = 0; k < kCrowdMaxBins; k++) {
+        const float e = edges[k < n_bins ? k : n_bins - 1u];
+        dc.e2[k] = e * e;
+    }
+    launch_accessible_points(dc.p, st);
+    launch_mask_free(dc.p, dc.free, st);
+    NbArgs scan = l.a;  // (the neighbour run has read its parts and its info)
+    scan.counts = dc.free;
+    scan.offsets = (unsigned long long *)R.row_offsets.p;
+    launch_neighbor_scan(scan, st);
+    launch_sort_flags(h, st);
+    RS_HIP(ctx, hipGetLastError());
+    RS_HIP(ctx, download(out_offsets, dc.dot_offsets, (c.N + 1) * 8, st));
+    RS_HIP(ctx, hipStreamSynchronize(st));
+    const uint64_t n_dots = out_offsets[c.N];
+    if (n_dots >= 0x100000000ull) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "2^32 or more accessible dots");
+    if (!out_counts || cap < n_dots)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_counts is NULL or holds fewer rows than out_dot_offsets[n]");
+    if (n_dots) {
+        if ((rc = reserve(ctx, R.crowd, n_dots * n_bins * 4))) return rc;
+        dc.counts = (uint32_t *)R.crowd.p;
+        launch_dot_crowding(dc, st);
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, download(out_counts, dc.counts, n_dots * n_bins * 4, st));
+    }
+    RS_HIP(ctx, download(out_free, dc.free, c.N * 4, st));
+    RS_HIP(ctx, download(out_sasa, dc.p.sasa, c.N * 4, st));
     RS_HIP(ctx, hipStreamSynchronize(st));
     return RSASA_OK;
 }
@@ -878,6 +945,35 @@ int rsasa_surface_components_batch(rsasa_context_t *ctx, const float *x, const f
     RS_ARGS(ctx, check_link(link));
     return cc_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, n_points, link,
                   out_dot_offsets, out_labels, labels_capacity, out_free, out_atom_sasa);
+}
+
+int rsasa_dot_crowding(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                       const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, const uint8_t *flags,
+                       const float *edges, uint32_t n_bins, uint64_t *out_dot_offsets, uint32_t *out_counts,
+                       size_t counts_capacity, uint32_t *out_free, float *out_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    RS_ARGS(ctx, check_points(n_atoms, x, y, z, radius, out_dot_offsets, n_points));
+    RS_ARGS(ctx, check_crowding(edges, n_bins));
+    return dc_run(ctx, Cols(x, y, z, radius, id, n_atoms), probe_radius, n_points, flags, edges, n_bins, out_dot_offsets,
+                  out_counts, counts_capacity, out_free, out_sasa);
+}
+
+int rsasa_dot_crowding_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                             const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                             size_t n_points, const uint8_t *flags, const float *edges, uint32_t n_bins,
+                             uint64_t *out_dot_offsets, uint32_t *out_counts, size_t counts_capacity, uint32_t *out_free,
+                             float *out_atom_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    size_t N;
+    RS_ARGS(ctx, check_offsets(structure_offsets, n_structures, N));
+    RS_ARGS(ctx, check_points(N, x, y, z, radius, out_dot_offsets, n_points));
+    RS_ARGS(ctx, check_crowding(edges, n_bins));
+    return dc_run(ctx, Cols(x, y, z, radius, id, structure_offsets, n_structures, N), probe_radius, n_points, flags, edges,
+                  n_bins, out_dot_offsets, out_counts, counts_capacity, out_free, out_atom_sasa);
 }
 
 int rsasa_half_sphere_exposure(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,

@@ -12,7 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import (ATOM_DTYPE, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS, RADIAL_MAX_CLASSES, WITHIN_CENTRE,
+from ._capi import (ATOM_DTYPE, CROWD_MAX_BINS, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS, RADIAL_MAX_CLASSES, WITHIN_CENTRE,
                     WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings, check, ptr)
 
 
@@ -389,6 +389,42 @@ class Context:
         structure (subtract dot_offsets[structure_offsets[s]] from a position to get one).  link None: default_link of
         the whole batch's radii."""
         return self._surface_components(x, y, z, radius, ids, probe_radius, n_points, link, structure_offsets)
+
+    # ---- dot crowding (how much protein lies around each accessible dot, by distance bin) ----
+    def _dot_crowding(self, x, y, z, radius, ids, probe_radius, n_points, edges, flags, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("dot_crowding", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        flags = _flag_bytes(flags, n)
+        edges = _f32(edges)
+        if edges.ndim != 1 or not 1 <= edges.shape[0] <= CROWD_MAX_BINS:
+            raise ValueError(f"edges must be a 1-D array of 1 to {CROWD_MAX_BINS} radii")
+        n_bins = edges.shape[0]
+        free, sasa = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+
+        def call(offsets, counts, cap):
+            return entry(probe_radius, n_points, ptr(flags), ptr(edges), n_bins, ptr(offsets), ptr(counts), cap,
+                         ptr(free), ptr(sasa))
+        # the first guess of the rows: proteins have 4 to 7 accessible dots per atom at 100 points
+        return self._sized_call(call, n, min(n_points, 16) * n, np.dtype((np.uint32, (n_bins,)))) + (free, sasa)
+
+    def dot_crowding(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100,
+                     edges=(6.0, 8.0, 10.0), flags=None):
+        """rsasa_dot_crowding: (dot_offsets uint64[N + 1], counts uint32[D, B], free uint32[N], sasa float32[N]).  The
+        rows of counts are the accessible dots in the order of surface_points() and of surface_components' labels: atom
+        i's dots are [dot_offsets[i], dot_offsets[i + 1]).  counts[d, b] is the number of atoms j with CROWD_PARTNER in
+        flags[j] - the dot's own atom included - whose float32 d2 to the dot lies in bin b, the smallest b with
+        d2 <= edges[b] * edges[b], evaluated as the header defines it (plain float32, so the counts can be checked for
+        equality).  edges: 1 to CROWD_MAX_BINS radii, finite, not negative, non-decreasing.  flags None: every atom is a
+        partner.  np.cumsum(counts, -1)[:, k] is the number of atoms within edges[k] of each dot; dot_means() averages a
+        per-dot column over the atoms.  free is the popcount of accessible_points, sasa equals calculate_sasa_soa."""
+        return self._dot_crowding(x, y, z, radius, ids, probe_radius, n_points, edges, flags)
+
+    def dot_crowding_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100,
+                           edges=(6.0, 8.0, 10.0), flags=None):
+        """rsasa_dot_crowding_batch: dot_crowding of every structure (one grid each, atoms of other structures never
+        count); dot_offsets and the rows run over the whole batch."""
+        return self._dot_crowding(x, y, z, radius, ids, probe_radius, n_points, edges, flags, structure_offsets)
 
     # ---- half-sphere exposure (how many partners lie on either side of an atom, within a cutoff of several cells) ----
     def _half_sphere_exposure(self, x, y, z, radius, ids, probe_radius, dirs, flags, cutoff, structure_offsets=_SINGLE):
@@ -795,6 +831,31 @@ HSE_CENTRE = 2
 
 RADIAL_PARTNER = 1  # flag bits of radial_counts (those of half_sphere_exposure)
 RADIAL_CENTRE = 2
+
+
+CROWD_PARTNER = 1  # flag bit of dot_crowding: the atom is counted
+
+
+def dot_means(dot_offsets, values) -> np.ndarray:
+    """float64[N]: for every atom the mean of a per-dot column (dot_crowding's cumulative counts at one edge, say, or
+    anything else with one entry per dot) over its dots [dot_offsets[i], dot_offsets[i + 1]), NaN for an atom without
+    dots.  Summed in float64 in dot order on the host."""
+    off = np.ascontiguousarray(dot_offsets, dtype=np.uint64).astype(np.int64)
+    v = np.asarray(values)
+    if off.ndim != 1 or off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("dot_offsets must be non-decreasing from 0")
+    if v.ndim != 1 or v.shape[0] != int(off[-1]):
+        raise ValueError(f"values must be a 1-D array of dot_offsets[-1] = {int(off[-1])} entries")
+    v = v.astype(np.float64)
+    out = np.full(off.shape[0] - 1, np.nan, np.float64)
+    for i in range(off.shape[0] - 1):
+        b, e = int(off[i]), int(off[i + 1])
+        if e > b:
+            total = 0.0
+            for x in v[b:e]:
+                total += float(x)
+            out[i] = total / (e - b)
+    return out
 
 
 def radial_density(counts, edges) -> np.ndarray:
