@@ -444,10 +444,11 @@ struct rsasa_context {
     size_t stream_sub_batches = 0; // a worker context of a stream of host batches: most sub-batches of a call (0: the default)
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
-    // rsasa_precompute_neighbors* and the point runs behind them - accessible points, exposure vectors, atom depth,
-    // surface components, contact counts, contact owners, group contacts - and the half-sphere exposure (neighbors.cpp).  A workspace of their own: device batches in
-    // flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls queue their work on `stream` behind whatever
-    // it holds.  What outlives a call is here: the workspace's and the cell array's sizes, the pinned block the device's
+    // The thirteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
+    // exposure vectors, atom depth, surface components, dot crowding, contact counts, contact owners, group contacts; and
+    // the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest atoms, radial counts.  A
+    // workspace of their own: device batches in flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls
+    // queue their work on `stream` behind whatever it holds.  What outlives a call is here: the workspace's and the cell array's sizes, the pinned block the device's
     // verdicts come back in, and the lattice in the reference's order (the SASA path's cached lattices reorder the points
     // above 128) with the point count it holds (0: none).
     Workspace nb_ws;
@@ -455,22 +456,24 @@ struct rsasa_context {
     uint64_t nb_cell_capacity = 0;
     DeviceBuffer pt_lattice;
     size_t pt_lattice_points = 0;
-    // The scratch of these calls.  Every one of them holds `mu` from its first line to its last and synchronises `stream`
-    // before it returns, so NOTHING here is live between calls: a call reserves what it uses (contents are not kept) and
-    // may find a buffer sized by another family.  Two members of one call never share a buffer; two families do.
+    // The scratch of these calls.  Every one of them runs under a frame (neighbors.cpp: Run) that holds `mu` from the end
+    // of the argument rules to the call's last line, and synchronises `stream` before it returns, so NOTHING here is live
+    // between calls: a call reserves what it uses through the frame (contents are not kept) and may find a buffer sized by
+    // another family.  Two members of one call never share a buffer; two families do.
     struct RunScratch {
         DeviceBuffer x, y, z, r, id, map;                                 // the uploaded columns and idx_map
         DeviceBuffer counts, offsets, parts, info, entries, spill, recs;  // the neighbour lists (NbArgs)
         DeviceBuffer masks, sasa;                                         // PtArgs::masks, ::sasa
-        DeviceBuffer free;         // accessible points per atom (exposure, depth, components, groups)
-        DeviceBuffer row_offsets;  // [N + 1]: where an atom's dots (components) or rows (groups) begin
+        DeviceBuffer free;         // accessible points per atom (exposure, depth, components, crowding, groups)
+        DeviceBuffer row_offsets;  // [N + 1]: where an atom's dots (components, crowding) or rows (groups) begin: pt_rows
         DeviceBuffer vectors, keys;                                       // exposure sums; nearest-dot keys
         DeviceBuffer parent, labels;                                      // union-find forest and labels, per dot
         DeviceBuffer covered, exclusive;                                  // contact counts, per list entry
         DeviceBuffer owned, owner;                                        // contact owners: per list entry; per point
         // group contacts: the labels, the lists in label order, own-group and row counts per atom, the rows
         DeviceBuffer group, sorted, sorted_group, own, nrows, groups, buried, only, self_free;
-        // half-sphere exposure: the directions and flags, the flags in cell-sorted order, the two counts per atom
+        // half-sphere exposure: the directions and flags, the flags in cell-sorted order, the two counts per atom.  flags
+        // and sorted_flags serve every family that takes flags (hs_flags); the radial counts leave class bits in the latter
         DeviceBuffer dirs, flags, sorted_flags, up, down;
         DeviceBuffer rows;  // the k nearest atoms: a row of k keys per centre (NnArgs::rows)
         // radial counts: the class bytes, the structures' offsets, the dense table of rows, the pair tables (RdArgs)

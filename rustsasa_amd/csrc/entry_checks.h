@@ -1,29 +1,13 @@
 // The argument rules of the neighbour-list and point-run entry points (neighbors.cpp), and the one description of their
-// input.  Plain host C++: no HIP, no context, nothing is written but N.  A rule returns the message of the first thing it
-// finds wrong, or null when the arguments stand; the entry points turn a message into RSASA_ERR_INVALID_ARGUMENT.
+// input.  Plain host C++: no HIP, no context, nothing is written but N and the Cols.  A rule returns the message of the
+// first thing it finds wrong, or null when the arguments stand; the entry points turn a message into
+// RSASA_ERR_INVALID_ARGUMENT.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 
 namespace rsasa {
-
-// The columns of a run in host memory: S structures, N atoms, structure s being atoms [so[s], so[s + 1]).
-struct Cols {
-    const float *x, *y, *z, *r;
-    const uint64_t *id;  // nullable
-    const uint32_t *so;
-    size_t S, N;
-    uint32_t one[2];  // `so` of a single structure
-    // a single structure of N atoms
-    Cols(const float *x, const float *y, const float *z, const float *r, const uint64_t *id, size_t N)
-        : x(x), y(y), z(z), r(r), id(id), so(one), S(1), N(N), one{0u, (uint32_t)N} {}
-    // the caller's structure_offsets, which check_offsets has passed and taken N from
-    Cols(const float *x, const float *y, const float *z, const float *r, const uint64_t *id, const uint32_t *so, size_t S, size_t N)
-        : x(x), y(y), z(z), r(r), id(id), so(so), S(S), N(N), one{} {}
-    Cols(const Cols &) = delete;  // (so may point into the object)
-    Cols &operator=(const Cols &) = delete;
-};
 
 // The shape of structure_offsets[0 .. n_structures]: non-decreasing from 0 to N, fewer than 2^31 - 1 atoms.
 inline const char *check_offsets(const uint32_t *so, size_t n_structures, size_t &N)
@@ -38,6 +22,42 @@ inline const char *check_offsets(const uint32_t *so, size_t n_structures, size_t
     if (N >= 0x7FFFFFFFull) return "more than 2^31 - 1 atoms";
     return nullptr;
 }
+
+// How an entry point names its atoms: a single structure of n atoms, or n structures by the caller's structure_offsets.
+struct Form {
+    bool batch;
+    const uint32_t *so;  // batch: structure_offsets[0 .. n]
+    size_t n;
+    static Form one(size_t n_atoms) { return {false, nullptr, n_atoms}; }
+    static Form many(const uint32_t *so, size_t n_structures) { return {true, so, n_structures}; }
+};
+
+// The columns of a run in host memory: S structures, N atoms, structure s being atoms [so[s], so[s + 1]).  Empty (S = N
+// = 0, no offsets) until fix() has passed.
+struct Cols {
+    const float *x, *y, *z, *r;
+    const uint64_t *id;  // nullable
+    const uint32_t *so = nullptr;
+    size_t S = 0, N = 0;
+    uint32_t one[2] = {0u, 0u};  // `so` of a single structure
+    Cols(const float *x, const float *y, const float *z, const float *r, const uint64_t *id) : x(x), y(y), z(z), r(r), id(id) {}
+    Cols(const Cols &) = delete;  // (so may point into the object)
+    Cols &operator=(const Cols &) = delete;
+    // Fixes N and the structures.  A single structure owns its offsets {0, n} and has no rule of its own; a batch points
+    // at the caller's, under check_offsets: on its message the Cols stays empty.
+    const char *fix(const Form &f)
+    {
+        if (!f.batch) {
+            one[1] = (uint32_t)f.n;
+            so = one; S = 1; N = f.n;
+            return nullptr;
+        }
+        const char *msg = check_offsets(f.so, f.n, N);
+        if (msg) N = 0;
+        else { so = f.so; S = f.n; }
+        return msg;
+    }
+};
 
 // The columns of N atoms.  rest: whatever else the call cannot do without is there - the caller's own test of the arrays
 // it needs always and of those that have an entry per atom (which may all be NULL when N is 0, as the columns may).

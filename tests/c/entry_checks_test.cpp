@@ -78,15 +78,34 @@ int main()
 
     // ---- the input's description: a single structure owns its offsets
     {
-        const Cols one(col, col, col, col, nullptr, 7);
-        if (one.S != 1 || one.N != 7 || one.so != one.one || one.so[0] != 0 || one.so[1] != 7) {
+        Cols one(col, col, col, col, nullptr);
+        const char *msg = one.fix(Form::one(7));
+        if (msg || one.S != 1 || one.N != 7 || one.so != one.one || one.so[0] != 0 || one.so[1] != 7) {
             std::printf("FAIL Cols of a single structure\n");
             failures++;
         }
-        const uint32_t so[3] = {0, 3, 7};
-        const Cols many(col, col, col, col, nullptr, so, 2, 7);
-        if (many.S != 2 || many.N != 7 || many.so != so) {
+        // (heap arrays of exactly the entries given, as in offsets(): one read past them is the sanitizer's)
+        const std::vector<uint32_t> so = {0, 3, 7};
+        Cols many(col, col, col, col, nullptr);
+        msg = many.fix(Form::many(so.data(), 2));
+        if (msg || many.S != 2 || many.N != 7 || many.so != so.data()) {
             std::printf("FAIL Cols of structure_offsets\n");
+            failures++;
+        }
+        const std::vector<uint32_t> falling = {0, 5, 4};
+        Cols bad(col, col, col, col, nullptr);
+        bad.N = 12345;
+        expect("Cols of falling offsets", bad.fix(Form::many(falling.data(), 2)), false, "structure_offsets must be non-decreasing");
+        if (bad.N != 0) {
+            std::printf("FAIL Cols of falling offsets: N = %zu, expected 0\n", bad.N);
+            failures++;
+        }
+        const std::vector<uint32_t> first = {0};
+        Cols none(col, col, col, col, nullptr);
+        none.N = 12345;
+        msg = none.fix(Form::many(first.data(), 0));
+        if (msg || none.S != 0 || none.N != 0 || none.so != first.data()) {
+            std::printf("FAIL Cols of no structure\n");
             failures++;
         }
     }
