@@ -44,7 +44,7 @@ extern "C" {
  * rsasa_atoms_within_batch; RSASA_NEAREST_MAX_K, rsasa_nearest_atoms, rsasa_nearest_atoms_batch;
  * RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS, rsasa_radial_counts, rsasa_radial_counts_batch;
  * rsasa_contact_owners, rsasa_contact_owners_batch; RSASA_CROWD_MAX_BINS, rsasa_dot_crowding,
- * rsasa_dot_crowding_batch. */
+ * rsasa_dot_crowding_batch; RSASA_ENCLOSE_MAX_DIRS, rsasa_dot_enclosure, rsasa_dot_enclosure_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -59,7 +59,7 @@ typedef enum rsasa_status {
     RSASA_ERR_BUFFER_TOO_SMALL = -8  /* rsasa_precompute_neighbors*, rsasa_contact_points*, rsasa_contact_owners*: out_entries is NULL or holds
                                         fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
                                         the same for its row buffers; rsasa_surface_components*: for out_labels;
-                                        rsasa_dot_crowding*: for out_counts;
+                                        rsasa_dot_crowding*: for out_counts; rsasa_dot_enclosure*: for out_blocked;
                                         rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries */
 } rsasa_status;
 
@@ -773,6 +773,115 @@ int rsasa_dot_crowding_batch(rsasa_context_t *ctx,
                              uint64_t *out_dot_offsets,
                              uint32_t *out_counts, size_t counts_capacity,
                              uint32_t *out_free, float *out_atom_sasa);
+
+/* ---- dot enclosure ------------------------------------------------------ */
+
+/* HOW ENCLOSED each point of the accessible surface is: per accessible dot the
+ * directions, of a fixed fan, in which a probe leaving the dot on a straight
+ * path is stopped by protein within a given length - the buriedness that
+ * pocket finders rank by.  A count of atoms by distance (rsasa_dot_crowding)
+ * does not see direction: a dot on a flat face over a thick slab and a dot in a
+ * narrow pocket have as many atoms within 10 A, but the first has a half-space
+ * open and the second almost nothing.
+ *
+ * Definition.  Take one structure, probe p, lattice
+ * s = rsasa_sphere_points(n_points) and directions
+ * u = rsasa_sphere_points(n_dirs), 1 <= n_dirs <= RSASA_ENCLOSE_MAX_DIRS.  Dots,
+ * their order and out_dot_offsets are exactly those of
+ * rsasa_surface_components and rsasa_dot_crowding.  Each atom j has a flag byte
+ * f_j: bit 0 (RSASA_ENCLOSE_PARTNER) - the atom is an obstacle; the other bits
+ * are ignored; flags == NULL: every atom is an obstacle.  reach = L is the
+ * length of a ray.  All arithmetic is float32, unfused, left to right.  For the
+ * dot (i, k), direction m and an obstacle j != i (by atom index: a coincident
+ * twin is an obstacle like any other) of the SAME structure:
+ *
+ *     R_i = r_i + p
+ *     q   = (c_i.x + R_i * s_k.x, c_i.y + R_i * s_k.y, c_i.z + R_i * s_k.z)
+ *     R_j = r_j + p;   R2 = R_j * R_j
+ *     dx = c_j.x - q.x                          (dy, dz alike)
+ *     d2 = dx * dx + dy * dy + dz * dz
+ *     t  = dx * u_m.x + dy * u_m.y + dz * u_m.z
+ *     j stops ray m  iff  t > 0  and
+ *         ( t <= L  ?  d2 - t * t <= R2
+ *                   :  ex = dx - L * u_m.x (ey, ez alike);
+ *                      ex * ex + ey * ey + ez * ez <= R2 )
+ *
+ * In words: the segment q + t u_m, 0 <= t <= L, meets the expanded sphere of j -
+ * its nearest point to c_j is the foot of the perpendicular or the far end.  The
+ * ray is the path of a probe CENTRE, so the obstacle is the expanded sphere, the
+ * one that defines the dots.  A sphere behind the start (t <= 0) stops nothing:
+ * accessible dots lie outside every other expanded sphere.
+ *
+ * The own atom i is not put through this test (its dot lies on its own sphere
+ * up to rounding).  It stops ray m iff it has the obstacle bit and
+ *
+ *     u_m.x * s_k.x + u_m.y * s_k.y + u_m.z * s_k.z < 0
+ *
+ * - the ray enters the sphere it starts on; a tangent ray is free; L plays no
+ * part.
+ *
+ * out_blocked[dot] is a uint32: bit m is set iff the own-atom rule or some
+ * obstacle stops ray m; bits >= n_dirs are 0.  The decisions are booleans OR-ed
+ * over the obstacles, so the words have no order and can be checked for
+ * equality.  A NaN anywhere fails its comparison and stops nothing:
+ *   - a NaN obstacle (coordinate or radius) stops no ray;
+ *   - the dots of an atom with a NaN coordinate or radius are stopped by no
+ *     other atom, whatever t > 0 gives;
+ *   - their own-atom bits stay as the lattice gives them (that rule reads only
+ *     u_m and s_k).
+ *
+ *   out_dot_offsets  [n + 1], as rsasa_surface_components writes it;
+ *   out_blocked      [blocked_capacity]: word d is dot d, lined up with
+ *                    out_labels of rsasa_surface_components and the rows of
+ *                    rsasa_dot_crowding;
+ *   out_free[i]      (nullable) the popcount of rsasa_accessible_points;
+ *   out_sasa[i]      (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Sizing, as rsasa_dot_crowding: out_dot_offsets is always written (on success
+ * and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_blocked is NULL or
+ * blocked_capacity (in dots) < out_dot_offsets[n], nothing else is written and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned: call once to size, allocate, call
+ * again.  A batch with 2^32 or more dots returns RSASA_ERR_INVALID_ARGUMENT.
+ *
+ * n_dirs must lie in [1, RSASA_ENCLOSE_MAX_DIRS]; reach must be finite and >= 0
+ * (-0.0 is 0); anything else returns RSASA_ERR_INVALID_ARGUMENT.  The remaining
+ * argument errors and the non-finite input rules are those of rsasa_atom_depth.
+ * No atoms: RSASA_OK with out_dot_offsets[0] = 0.  The call holds 4 bytes per dot
+ * on the device; a failed reservation returns RSASA_ERR_OUT_OF_MEMORY and the
+ * context stays usable.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed.  8
+ * bytes per atom and 4 per dot cross the link (and 4 per atom each for
+ * out_free and out_sasa). */
+#define RSASA_ENCLOSE_PARTNER 1
+#define RSASA_ENCLOSE_MAX_DIRS 32
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).  flags:
+ * [n_atoms] or NULL; out_dot_offsets: [n_atoms + 1]; out_blocked:
+ * [blocked_capacity]; out_free, out_sasa: [n_atoms] or NULL. */
+int rsasa_dot_enclosure(rsasa_context_t *ctx,
+                        const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms,
+                        float probe_radius, size_t n_points,
+                        const uint8_t *flags, float reach, uint32_t n_dirs,
+                        uint64_t *out_dot_offsets,
+                        uint32_t *out_blocked, size_t blocked_capacity,
+                        uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form: n_structures independent structures concatenated as in
+ * rsasa_calculate_sasa_batch (one grid each; an empty structure is legal);
+ * atoms of other structures stop nothing.  flags runs over
+ * structure_offsets[n_structures] atoms; out_dot_offsets is batch-global. */
+int rsasa_dot_enclosure_batch(rsasa_context_t *ctx,
+                              const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id,
+                              const uint32_t *structure_offsets, size_t n_structures,
+                              float probe_radius, size_t n_points,
+                              const uint8_t *flags, float reach, uint32_t n_dirs,
+                              uint64_t *out_dot_offsets,
+                              uint32_t *out_blocked, size_t blocked_capacity,
+                              uint32_t *out_free, float *out_atom_sasa);
 
 /* ---- half-sphere exposure ----------------------------------------------- */
 

@@ -263,6 +263,25 @@ struct DcArgs {
     uint32_t *counts;                   // [dot_offsets[n_atoms]][n_bins]: every row is written
 };
 
+// ---- dot enclosure (enclosure.hip, rsasa_dot_enclosure*) ----
+// A finished point run (p.masks written, in input order), the grid it ran on and a flag byte per atom: the accessible
+// dots numbered as CcArgs numbers them and, per dot, the directions of a fixed fan in which the probe is stopped.
+constexpr uint32_t kEncloseDirs = 32;   // the directions of the fan at most: a bit each of a dot's word
+struct DeDir {                          // direction m of the fan, as the kernel reads it (32 bytes, one scalar load)
+    float ux, uy, uz, pad0;             // u_m of generate_sphere_points(n_dirs)
+    float lx, ly, lz, pad1;             // reach * u_m, per component (one float32 product each): the ray's far end
+};
+struct DeArgs {
+    PtArgs p;                           // p.masks, p.words: the masks k_accessible_points wrote; p.sasa as there
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_mask_free)
+    const unsigned long long *dot_offsets;  // [n_atoms + 1] exclusive scan of free: atom i's dots are [dot_offsets[i], dot_offsets[i + 1])
+    const uint8_t *sorted_flags;        // [n_atoms] HsArgs::sorted_flags (k_sort_flags): bit 0 - the atom is an obstacle
+    uint32_t n_dirs;                    // 1 .. kEncloseDirs
+    float reach, reach2;                // L and L * L (one float32 product; may overflow to +inf, underflow to 0)
+    DeDir dir[kEncloseDirs];            // [n_dirs .. 32) are zero and never read
+    uint32_t *blocked;                  // [dot_offsets[n_atoms]]: every word is written
+};
+
 // ---- half-sphere exposure (hse.hip, rsasa_half_sphere_exposure*) ----
 // A binned batch (no neighbour lists) with a direction and a flag byte per atom: per centre the partners of its own
 // structure within the cutoff, split by the side of the plane through the centre that is normal to its direction.
@@ -419,6 +438,8 @@ void launch_atom_depth(const DpArgs &d, hipStream_t stream);
 void launch_components(const CcArgs &c, hipStream_t stream);
 // The rows of the dots (crowding.hip) from those masks and counts, with DcArgs::dot_offsets and ::sorted_flags.
 void launch_dot_crowding(const DcArgs &d, hipStream_t stream);
+// The blocked directions of the dots (enclosure.hip) from those masks and counts, with DeArgs::dot_offsets and ::sorted_flags.
+void launch_dot_enclosure(const DeArgs &d, hipStream_t stream);
 // The half-sphere counts (hse.hip) on a binned batch: the flags in cell-sorted order, then up[] and down[].
 void launch_half_sphere(const HsArgs &h, hipStream_t stream);
 // The keys k_neighbor_fill / k_within_fill stage per list in LDS: what NbArgs::stage is set to for their runs.

@@ -444,8 +444,9 @@ struct rsasa_context {
     size_t stream_sub_batches = 0; // a worker context of a stream of host batches: most sub-batches of a call (0: the default)
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
-    // The thirteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
-    // exposure vectors, atom depth, surface components, dot crowding, contact counts, contact owners, group contacts; and
+    // The fourteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
+    // exposure vectors, atom depth, surface components, dot crowding, dot enclosure, contact counts, contact owners,
+    // group contacts; and
     // the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest atoms, radial counts.  A
     // workspace of their own: device batches in flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls
     // queue their work on `stream` behind whatever it holds.  What outlives a call is here: the workspace's and the cell array's sizes, the pinned block the device's
@@ -464,8 +465,8 @@ struct rsasa_context {
         DeviceBuffer x, y, z, r, id, map;                                 // the uploaded columns and idx_map
         DeviceBuffer counts, offsets, parts, info, entries, spill, recs;  // the neighbour lists (NbArgs)
         DeviceBuffer masks, sasa;                                         // PtArgs::masks, ::sasa
-        DeviceBuffer free;         // accessible points per atom (exposure, depth, components, crowding, groups)
-        DeviceBuffer row_offsets;  // [N + 1]: where an atom's dots (components, crowding) or rows (groups) begin: pt_rows
+        DeviceBuffer free;         // accessible points per atom (exposure, depth, components, crowding, enclosure, groups)
+        DeviceBuffer row_offsets;  // [N + 1]: where an atom's dots (components, crowding, enclosure) or rows (groups) begin: pt_rows
         DeviceBuffer vectors, keys;                                       // exposure sums; nearest-dot keys
         DeviceBuffer parent, labels;                                      // union-find forest and labels, per dot
         DeviceBuffer covered, exclusive;                                  // contact counts, per list entry
@@ -479,6 +480,7 @@ struct rsasa_context {
         // radial counts: the class bytes, the structures' offsets, the dense table of rows, the pair tables (RdArgs)
         DeviceBuffer classes, so, table, pairs;
         DeviceBuffer crowd;  // dot crowding: a row of n_bins counts per dot (DcArgs::counts)
+        DeviceBuffer enclose;  // dot enclosure: a word of blocked directions per dot (DeArgs::blocked)
     } run;
 };
 

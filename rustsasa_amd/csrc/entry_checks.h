@@ -135,6 +135,16 @@ inline const char *check_crowding(const float *edges, uint32_t n_bins)
     return check_edges(edges, n_bins);
 }
 
+// The fan of the dot enclosure: 1 .. RSASA_ENCLOSE_MAX_DIRS directions - a dot's word of k_dot_enclosure has a bit for
+// each - and a reach that is finite and not negative (-0.0 is 0).
+constexpr uint32_t kEncloseMaxDirs = 32;
+inline const char *check_enclosure(float reach, uint32_t n_dirs)
+{
+    if (n_dirs < 1u || n_dirs > kEncloseMaxDirs) return "n_dirs must be in [1, 32]";
+    if (!(reach >= 0.0f) || std::isinf(reach)) return "reach must be finite and not negative";
+    return nullptr;
+}
+
 // The class bytes of N atoms (nullable: every atom is class 0): every one below n_classes, on any atom.
 inline const char *check_classes(const uint8_t *classes, size_t N, uint32_t n_classes)
 {

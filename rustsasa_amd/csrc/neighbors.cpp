@@ -1,11 +1,11 @@
-// Host side of the thirteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
+// Host side of the fourteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
 // batch pair of include/rustsasa_amd.h: the neighbour lists (rsasa_precompute_neighbors*); the point runs built on
-// them - accessible points, exposure vectors, atom depth, surface components, dot crowding, contact counts, contact
-// owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
+// them - accessible points, exposure vectors, atom depth, surface components, dot crowding, dot enclosure, contact
+// counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
 // atoms, radial counts.  The grid is built by the SASA path's kernels (nb_grid, and hs_grid for the runs on the grid
 // alone), then neighbors.hip counts, scans and fills the lists (nb_count, nb_fill).  A point run keeps the lists on the
 // device: every family shares one prologue (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and
-// adds its own kernels of points.hip, depth.hip, components.hip or crowding.hip and its own downloads.
+// adds its own kernels of points.hip, depth.hip, components.hip, crowding.hip or enclosure.hip and its own downloads.
 // Every family is one function (*_run) behind its two entry points, which only forward to it: the single form as
 // Form::one(n_atoms), the batch form as Form::many(structure_offsets, n_structures).  The function opens with the rules
 // - entry_open: the context, N and the Cols (entry_checks.h: Cols::fix), n_points, the columns; then the family's own -
@@ -537,6 +537,59 @@ int dc_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     return RSASA_OK;
 }
 
+// ---- dot enclosure (rsasa_dot_enclosure*) ----
+
+// One run of the dot enclosure: dc_run's dots and sorted flags; the fan of n_dirs directions is computed here
+// (generate_sphere_points, what rsasa_sphere_points returns) and travels in the kernel's arguments with the reach, its
+// square and the rays' far ends reach * u_m; the caller's buffer is checked against out_offsets[N], then k_dot_enclosure
+// fills a word per dot.  8 bytes per atom and 4 per dot come back (and 4 per atom each for the counts and the values,
+// if asked).
+int de_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id, Form form,
+           float probe, size_t n_points, const uint8_t *flags, float reach, uint32_t n_dirs, uint64_t *out_offsets,
+           uint32_t *out_blocked, size_t cap, uint32_t *out_free, float *out_sasa)
+{
+    static_assert(kEncloseMaxDirs == RSASA_ENCLOSE_MAX_DIRS, "the header's bound is the kernel's bound");
+    static_assert(kEncloseMaxDirs == kEncloseDirs && kEncloseDirs == 32, "a direction per bit of a dot's word");
+    static_assert(sizeof(DeArgs::dir) == kEncloseMaxDirs * 32, "32 bytes per direction");
+    static_assert(sizeof(DeArgs) <= 4096, "kernel arguments");
+    Cols c(x, y, z, r, id);
+    if (int rc = entry_open(ctx, c, form, &n_points, out_offsets, true)) return rc;
+    RS_ARGS(ctx, check_enclosure(reach, n_dirs));
+    Run f(ctx);
+    if (!f.open(c.N, out_offsets)) return f.rc;
+    int rc;
+    Lists l;
+    DeArgs de{};
+    HsArgs h{};
+    if ((rc = pt_count(f, c, probe, nullptr, l)) || (rc = pt_prepare(f, l, n_points, true, out_sasa != nullptr, de.p)) ||
+        (rc = f.reserve(f.R.free, c.N * 4, de.free)) || (rc = f.reserve(f.R.row_offsets, (c.N + 1) * 8, de.dot_offsets)) ||
+        (rc = hs_flags(f, c.N, flags, h)))
+        return rc;
+    h.b = de.p.b;
+    de.sorted_flags = h.sorted_flags;
+    de.n_dirs = n_dirs;
+    de.reach = reach + 0.0f;  // (-0.0 is 0)
+    de.reach2 = de.reach * de.reach;
+    float ux[kEncloseMaxDirs], uy[kEncloseMaxDirs], uz[kEncloseMaxDirs];
+    generate_sphere_points(n_dirs, ux, uy, uz);
+    for (uint32_t m = 0; m < n_dirs; m++)
+        de.dir[m] = DeDir{ux[m], uy[m], uz[m], 0.0f, de.reach * ux[m], de.reach * uy[m], de.reach * uz[m], 0.0f};
+    uint64_t n_dots;
+    if ((rc = pt_dots(f, l, de.p, de.free, &h, out_offsets, n_dots))) return rc;
+    if (!out_blocked || cap < n_dots)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_blocked is NULL or holds fewer words than out_dot_offsets[n]");
+    if (n_dots) {
+        if ((rc = f.reserve(f.R.enclose, n_dots * 4, de.blocked))) return rc;
+        launch_dot_enclosure(de, f.st);
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, download(out_blocked, de.blocked, n_dots * 4, f.st));
+    }
+    RS_HIP(ctx, download(out_free, de.free, c.N * 4, f.st));
+    RS_HIP(ctx, download(out_sasa, de.p.sasa, c.N * 4, f.st));
+    RS_HIP(ctx, hipStreamSynchronize(f.st));
+    return RSASA_OK;
+}
+
 // ---- contact counts (rsasa_contact_points*) ----
 
 // One run of the contact counts: the lists, sized and copied out as by nb_run, and k_contact_points' counts of every
@@ -922,6 +975,25 @@ int rsasa_dot_crowding_batch(rsasa_context_t *ctx, const float *x, const float *
 {
     return dc_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, flags, edges,
                     n_bins, out_dot_offsets, out_counts, counts_capacity, out_free, out_atom_sasa);
+}
+
+int rsasa_dot_enclosure(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, const uint8_t *flags,
+                        float reach, uint32_t n_dirs, uint64_t *out_dot_offsets, uint32_t *out_blocked,
+                        size_t blocked_capacity, uint32_t *out_free, float *out_sasa)
+{
+    return de_run(ctx, x, y, z, radius, id, Form::one(n_atoms), probe_radius, n_points, flags, reach, n_dirs, out_dot_offsets,
+                    out_blocked, blocked_capacity, out_free, out_sasa);
+}
+
+int rsasa_dot_enclosure_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                              size_t n_points, const uint8_t *flags, float reach, uint32_t n_dirs,
+                              uint64_t *out_dot_offsets, uint32_t *out_blocked, size_t blocked_capacity, uint32_t *out_free,
+                              float *out_atom_sasa)
+{
+    return de_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, flags, reach,
+                    n_dirs, out_dot_offsets, out_blocked, blocked_capacity, out_free, out_atom_sasa);
 }
 
 int rsasa_half_sphere_exposure(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,

@@ -1,5 +1,5 @@
 // The shell sweep of the wave-per-atom kernels that search the grid beyond the neighbour reach (device only, gfx950
-// only): its frame (sh_frame), its driver (sh_sweep) and the steps the driver is made of.  Eight kernels sweep this way,
+// only): its frame (sh_frame), its driver (sh_sweep) and the steps the driver is made of.  Nine kernels sweep this way,
 // each with its own work per batch of atoms (the driver's `visit`) and its own stop rule (its `after`).
 // Run by sh_sweep:
 //   k_half_sphere (hse.hip)            sh_cutoff_reached(c2) of cutoff_sweep.h
@@ -7,6 +7,8 @@
 //   k_radial_counts (radial.hip)       sh_cutoff_reached(the last squared edge)
 //   k_dot_crowding (crowding.hip)      the last squared edge <= ((s - 1.5) h)^2, s >= 2: the partners are counted around
 //                                      the dots of i, which lie up to h from c_i (written out it was not timed)
+//   k_dot_enclosure (enclosure.hip)    reach^2 <= ((s - 2.5) h)^2, s >= 3: rays from the dots of i, up to h from c_i, are
+//                                      stopped by spheres of up to h around the atoms (written out it was not timed)
 // With the driver's three loops written out, because run by sh_sweep they measured slower on the MI355X at the same
 // registers, LDS and (within a few) instructions - the table is profiles/sweep_driver_ab.txt; their instruction streams
 // are the ones they had before the driver existed.  A change to sh_sweep is made in these three places too:
@@ -38,7 +40,7 @@
 // rounded sum of a radius and the probe), probe >= 0, and every |coordinate| <= 65536 h - a coordinate's ulp is at most
 // h / 128 and t' < 2^18, so t' is within 1/16 of the exact (x - min) / h, and |x_j - x_i| > (s - 1/8) h.  Every dot of j
 // lies within R_j <= h of c_j, and a dot q = c_j + R_j * s_k and a difference of two points carry a few roundings of at
-// most h / 128 each.  The stop rules of the eight kernels follow from this; without the margins every one of them sweeps
+// most h / 128 each.  The stop rules of the nine kernels follow from this; without the margins every one of them sweeps
 // until the shells cover the grid (ShCell::s_last), which is always exact.
 #pragma once
 #include "device_utils.h"

@@ -12,8 +12,9 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import (ATOM_DTYPE, CROWD_MAX_BINS, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS, RADIAL_MAX_CLASSES, WITHIN_CENTRE,
-                    WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings, check, ptr)
+from ._capi import (ATOM_DTYPE, CROWD_MAX_BINS, ENCLOSE_MAX_DIRS, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS,
+                    RADIAL_MAX_CLASSES, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings, check,
+                    ptr)
 
 
 def device_count() -> int:
@@ -426,6 +427,40 @@ class Context:
         count); dot_offsets and the rows run over the whole batch."""
         return self._dot_crowding(x, y, z, radius, ids, probe_radius, n_points, edges, flags, structure_offsets)
 
+    # ---- dot enclosure (in which directions a probe leaving an accessible dot is stopped by protein) ----
+    def _dot_enclosure(self, x, y, z, radius, ids, probe_radius, n_points, n_dirs, reach, flags, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("dot_enclosure", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        flags = _flag_bytes(flags, n)
+        n_dirs = int(n_dirs)
+        if not 0 <= n_dirs < 2 ** 32:
+            raise ValueError("n_dirs must fit an unsigned 32-bit integer")
+        free, sasa = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+
+        def call(offsets, blocked, cap):
+            return entry(probe_radius, n_points, ptr(flags), reach, n_dirs, ptr(offsets), ptr(blocked), cap, ptr(free), ptr(sasa))
+        return self._sized_call(call, n, min(n_points, 16) * n, np.uint32) + (free, sasa)
+
+    def dot_enclosure(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, n_dirs: int = 30,
+                      reach: float = 10.0, flags=None):
+        """rsasa_dot_enclosure: (dot_offsets uint64[N + 1], blocked uint32[D], free uint32[N], sasa float32[N]).  The
+        words of blocked are the accessible dots in the order of surface_points(), of surface_components' labels and of
+        dot_crowding's rows.  Bit m of blocked[d] is set when a probe centre leaving dot d along direction m of
+        sphere_points(n_dirs) meets, within `reach`, the expanded sphere (radius + probe_radius) of an atom j with
+        ENCLOSE_PARTNER in flags[j], or enters the dot's own atom's; the float32 test is the header's, so the words can
+        be checked for equality.  n_dirs: 1 to ENCLOSE_MAX_DIRS; reach finite and not negative; flags None: every atom
+        is an obstacle.  enclosure_fraction() turns the words into the blocked share, escape_vectors() into the way
+        out; dot_means() averages a fraction over the atoms.  free is the popcount of accessible_points, sasa equals
+        calculate_sasa_soa."""
+        return self._dot_enclosure(x, y, z, radius, ids, probe_radius, n_points, n_dirs, reach, flags)
+
+    def dot_enclosure_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100,
+                            n_dirs: int = 30, reach: float = 10.0, flags=None):
+        """rsasa_dot_enclosure_batch: dot_enclosure of every structure (one grid each, atoms of other structures stop
+        nothing); dot_offsets and the words run over the whole batch."""
+        return self._dot_enclosure(x, y, z, radius, ids, probe_radius, n_points, n_dirs, reach, flags, structure_offsets)
+
     # ---- half-sphere exposure (how many partners lie on either side of an atom, within a cutoff of several cells) ----
     def _half_sphere_exposure(self, x, y, z, radius, ids, probe_radius, dirs, flags, cutoff, structure_offsets=_SINGLE):
         (x, *_), entry = self._entry("half_sphere_exposure", x, y, z, radius, ids, structure_offsets)
@@ -836,6 +871,39 @@ RADIAL_CENTRE = 2
 CROWD_PARTNER = 1  # flag bit of dot_crowding: the atom is counted
 
 
+ENCLOSE_PARTNER = 1  # flag bit of dot_enclosure: the atom is an obstacle
+
+
+def _blocked_bits(blocked, n_dirs):
+    """bool[D, n_dirs]: the bits of dot_enclosure's words, checked."""
+    b = np.asarray(blocked)
+    n_dirs = int(n_dirs)
+    if not 1 <= n_dirs <= ENCLOSE_MAX_DIRS:
+        raise ValueError(f"n_dirs must lie in [1, {ENCLOSE_MAX_DIRS}]")
+    if b.ndim != 1 or b.dtype != np.uint32:
+        raise ValueError("blocked must be a 1-D uint32 array")
+    if n_dirs < 32 and (b >> np.uint32(n_dirs)).any():
+        raise ValueError("blocked has bits set at or above n_dirs")
+    return ((b[:, None] >> np.arange(n_dirs, dtype=np.uint32)[None, :]) & np.uint32(1)).astype(bool)
+
+
+def enclosure_fraction(blocked, n_dirs) -> np.ndarray:
+    """float64[D]: the share of the n_dirs directions of dot_enclosure that are blocked, popcount / n_dirs - 0 on an open
+    knob, 1 for a dot that is sealed in.  dot_means() averages it over the atoms."""
+    return _blocked_bits(blocked, n_dirs).sum(axis=1).astype(np.float64) / int(n_dirs)
+
+
+def escape_vectors(blocked, n_dirs) -> np.ndarray:
+    """float64[D, 3]: for every dot the sum of the FREE directions of sphere_points(n_dirs) - the way out of a pocket;
+    zero for a dot that is sealed in.  Summed in float64 in direction order on the host."""
+    free = ~_blocked_bits(blocked, n_dirs)
+    u = np.stack([np.asarray(a, np.float64) for a in sphere_points(int(n_dirs))], -1)
+    out = np.zeros((free.shape[0], 3), np.float64)
+    for m in range(int(n_dirs)):
+        out[free[:, m]] += u[m]
+    return out
+
+
 def dot_means(dot_offsets, values) -> np.ndarray:
     """float64[N]: for every atom the mean of a per-dot column (dot_crowding's cumulative counts at one edge, say, or
     anything else with one entry per dot) over its dots [dot_offsets[i], dot_offsets[i + 1]), NaN for an atom without
@@ -1161,5 +1229,6 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 
 
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
+           "ENCLOSE_MAX_DIRS", "ENCLOSE_PARTNER", "enclosure_fraction", "escape_vectors",
            "contact_areas", "group_areas", "owner_areas", "sas_volume", "residue_depth", "default_link", "component_table", "split_sasa",
            "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
