@@ -125,10 +125,13 @@ TIE_DX = 7.3
 TIE_KINDS = ("last", "inner", "duplicate", "below")
 
 
-def tie_geometry(probe=PROBE, partner_r=1.5, dx=TIE_DX):
-    """(xyz [2, 3] float32, r, q, edge): the owner and a partner moved from the owner's dot TIE_DOT along x alone:
-    d2 = fl(ddx * ddx) with ddx = fl(c_j.x - q.x), and edge = |ddx| ties with it exactly."""
+def tie_geometry(probe=PROBE, partner_r=1.5, dx=TIE_DX, centre=None):
+    """(xyz [2, 3] float32, r, q, edge): the owner (at `centre`, float32; None: TIE_OWNER's) and a partner moved from
+    the owner's dot TIE_DOT along x alone: d2 = fl(ddx * ddx) with ddx = fl(c_j.x - q.x), and edge = |ddx| ties with it
+    exactly."""
     c, r = TIE_OWNER
+    if centre is not None:
+        c = np.asarray(centre, F)
     m = np.zeros((1, TIE_POINTS), bool)
     m[0, TIE_DOT] = True
     _, qx, qy, qz = dm.dots_of(c[:1], c[1:2], c[2:], np.array([r], F), m, probe, TIE_POINTS)
@@ -164,14 +167,28 @@ LAST_EDGE = 5.0     # = (4 - 1.5) * 2: the rule is met after shell 4 with equali
 LAST_POINTS = 100
 
 
+LAST_SHELLS = (2, 3, 4)     # 2: the rule's clamp - the first shell after which it may stop a sweep
+LAST_PARTNER_RADIUS = {2: 0.25, 3: 1.25, 4: 1.25}   # (at shell 2 the partner lies 1 from the dot: R_j = 0.75 leaves it free)
+
+
+def last_edges(shell):
+    """The edges of last_shell(shell): the last one (shell - 1.5) h with h = 2, which the rule meets with equality."""
+    last = (shell - 1.5) * 2.0
+    return (2.0, 4.0, last) if shell == LAST_SHELL else (last / 4, last / 2, last)
+
+
 @functools.lru_cache(maxsize=None)
-def last_shell():
+def last_shell(shell=LAST_SHELL):
     """hse_cases.edge()'s grid (cell size exactly 2: probe 0.5, largest radius 1.5, atoms at 0 and 80 fix it), last edge
     5 = (4 - 1.5) h: the stop rule is met, with equality, after shell 4.  Owner `hi` sits one ulp under a cell's upper
     boundary on every axis, owner `lo` exactly on a lower one; both have radius 1.5 (R = h) and every point free.  For
     both, along +x, -x, +y, -y, +z, -z: the owner's outermost dot that way, and a partner moved 5 on along that axis
     alone - an exact tie at the last edge, up to 7 from the owner: in shell 4, the last one swept, on the side the owner
-    leans to.  info: hi, lo, ties = [(owner, dot rank, partner)]."""
+    leans to.  info: hi, lo, ties = [(owner, dot rank, partner)].
+    shell 3 and 2 (the clamp s >= 2): the same with the last edge (shell - 1.5) h = 3 and 1 and the partners moved that
+    far; at shell 2 the partners have radius 0.25, so that the dot 1 away from their centre stays accessible (the owners
+    keep every point: `dot rank` is the point's number at every shell)."""
+    last = last_edges(shell)[-1]
     eps = F(40.0) - np.nextafter(F(40.0), F(0.0))
     hi, lo = np.full(3, F(40.0) - eps, F), np.full(3, 20.0, F)
     pts, ties = [np.zeros(3, F), np.full(3, hc.EDGE_BOX, F), hi, lo], []
@@ -183,14 +200,14 @@ def last_shell():
             for sign in (1.0, -1.0):
                 k = int(np.argmax(sign * q[:, axis].astype(np.float64)))
                 p = q[k].copy()
-                p[axis] = q[k, axis] + F(sign * LAST_EDGE)
+                p[axis] = q[k, axis] + F(sign * last)
                 ties.append((o_idx, k, len(pts)))
                 pts.append(p)
     xyz = np.array(pts, F)
-    r = np.full(len(xyz), 1.25, F)
+    r = np.full(len(xyz), LAST_PARTNER_RADIUS[shell], F)
     r[[0, 1, 2, 3]] = 1.5
-    return _case("last_shell", [(xyz, r)], n_points=LAST_POINTS, edges=(2.0, 4.0, LAST_EDGE), probe=0.5,
-                 info=dict(hi=2, lo=3, ties=ties))
+    return _case("last_shell" if shell == LAST_SHELL else "last_shell_%d" % shell, [(xyz, r)], n_points=LAST_POINTS,
+                 edges=last_edges(shell), probe=0.5, info=dict(hi=2, lo=3, ties=ties, shell=shell))
 
 
 def reach_edges(h, shells):

@@ -124,15 +124,26 @@ def _dots(c):
     return np.stack([qx, qy, qz], -1)
 
 
+LAST_SHELLS = (3, 4, 5)     # 3: the rule's clamp - the first shell after which it may stop a sweep
+
+
+def last_reach(shell):
+    """(shell - 2.5) h with h = 2: the reach that the rule meets, with equality, after `shell` shells."""
+    return (shell - 2.5) * 2.0
+
+
 @functools.lru_cache(maxsize=None)
-def last_shell():
+def last_shell(shell=LAST_SHELL):
     """hse_cases.edge()'s grid (cell size exactly 2: probe 0.5, largest radius 1.5, atoms at 0 and 80 fix it), reach
     5 = (5 - 2.5) h: the stop rule is met, with equality, after shell 5.  Owner `hi` sits one ulp under a cell's upper
     boundary on every axis, owner `lo` exactly on a lower one; both have radius 1.5 (R = h) and every point free.  For
     hi along +x, +y, +z and for lo along -x, -y, -z - the side the owner leans to; on the other side shell 5 is out of
     any ray's reach -: the dot k and the direction m that lean that way most, and an obstacle of radius 1.5 (R_j = h)
     whose centre lies LAST_INSIDE beyond the far end of that ray along the axis, so the end is inside its sphere; its
-    cell is five from the owner's.  info: hi, lo, rays = [(owner, dot rank k, direction m, obstacle)]."""
+    cell is five from the owner's.  info: hi, lo, rays = [(owner, dot rank k, direction m, obstacle)].
+    shell 4 and 3 (the clamp s >= 3): the same with the reach (shell - 2.5) h = 3 and 1 = h / 2; the obstacle's cell is
+    four and three from the owner's."""
+    reach = last_reach(shell)
     hi, lo = _owners()
     u = em.directions(N_DIRS).astype(np.float64)
     pts, rays = [np.zeros(3, F), np.full(3, hc.EDGE_BOX, F), hi, lo], []
@@ -141,13 +152,13 @@ def last_shell():
         for axis in range(3):
             k = int(np.argmax(sign * q[:, axis].astype(np.float64)))
             m = int(np.argmax(sign * u[:, axis]))
-            p = q[k].astype(np.float64) + LAST_REACH * u[m]
+            p = q[k].astype(np.float64) + reach * u[m]
             p[axis] += sign * LAST_INSIDE
             rays.append((o_idx, k, m, len(pts)))
             pts.append(p.astype(F))
     xyz = np.array(pts, F)
-    return _case("last_shell", [(xyz, np.full(len(xyz), 1.5, F))], n_points=LAST_POINTS, reach=LAST_REACH, probe=0.5,
-                 info=dict(hi=2, lo=3, rays=rays))
+    return _case("last_shell" if shell == LAST_SHELL else "last_shell_%d" % shell, [(xyz, np.full(len(xyz), 1.5, F))],
+                 n_points=LAST_POINTS, reach=reach, probe=0.5, info=dict(hi=2, lo=3, rays=rays, shell=shell))
 
 
 # ---- the prefilter -------------------------------------------------------------------------------------------------------

@@ -228,10 +228,11 @@ def stop_shell(L, h, s_last, margins, early=False):
 
 
 def sweep_blocked(x, y, z, r, mask, probe, n_points, n_dirs, reach, flags, sample, margins=None, early=False, cuts=True,
-                  **switches):
+                  abs_term=True, **switches):
     """(words {atom: uint32[free]}, stop int64[len(sample)], by_rule bool[...], shells [{shell: uint32[free]}]) for the
     dots of the atoms `sample` of ONE structure, swept as the kernel sweeps them: the owner dropped by its position,
-    the staging cut and the lane cut where the margins hold (cuts=False: neither).  shells[n][s]: the bits that the
+    the staging cut and the lane cut where the margins hold (cuts=False: neither; abs_term=False: the staging cut
+    without its absolute h / 64 - a kernel that trusted the relative slack alone).  shells[n][s]: the bits that the
     obstacles of shell s set on the dots of sample[n] (the own-atom bits are in no shell)."""
     x, y, z, r = (np.ascontiguousarray(a, F) for a in (x, y, z, r))
     n = len(x)
@@ -264,7 +265,7 @@ def sweep_blocked(x, y, z, r, mask, probe, n_points, n_dirs, reach, flags, sampl
                         with np.errstate(invalid="ignore", over="ignore", under="ignore"):
                             ddx, ddy, ddz = x[j] - x[i], y[j] - y[i], z[j] - z[i]
                             dd2 = ddx * ddx + ddy * ddy + ddz * ddz
-                            far = ((L + R[i]) + R[j]) * SLACK + h64
+                            far = ((L + R[i]) + R[j]) * SLACK + (h64 if abs_term else F(0.0))
                             far2 = far * far
                             j = j[~(far2 >= F(1e-30)) | (dd2 <= far2)]
                             near = (L + R[j]) * SLACK

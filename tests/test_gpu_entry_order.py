@@ -2,8 +2,8 @@
 verdicts: every call here breaks two rules at once and must be answered with the earlier rule's message.  The order is
 resolve_ctx, the structure offsets (batch forms), n_points (point families), the columns and required outputs, then the
 family's own rules - k before cutoff for the nearest atoms; n_classes, n_bins, the edges, then the class bytes for the
-radial counts.  All 13 families, single and batch form, through the C ABI (_capi) on one context.  No call passes its
-rules, so no kernel is launched."""
+radial counts; n_dirs before reach for the dot enclosure.  All 14 families, single and batch form, through the C ABI
+(_capi) on one context.  No call passes its rules, so no kernel is launched."""
 import numpy as np
 import pytest
 
@@ -40,8 +40,8 @@ class Args:
         self.p = p
         self.v = dict(x=p["x"], y=p["y"], z=p["z"], r=p["r"], id=None, group=p["group"], so=p["so"], n_points=100,
                       link=1.0, cutoff=8.0, k=2, flags=None, dirs=None, classes=p["classes"], n_classes=2, edges=p["edges"],
-                      n_bins=2, active=None, n_active=0, out_offsets=p["o64"], out_a=p["o32a"], out_b=p["o32b"],
-                      out_c=p["o32c"], out_d=p["o32d"], out_e=p["o32e"], out_f=p["f32a"], cap=16)
+                      n_bins=2, reach=10.0, n_dirs=30, active=None, n_active=0, out_offsets=p["o64"], out_a=p["o32a"],
+                      out_b=p["o32b"], out_c=p["o32c"], out_d=p["o32d"], out_e=p["o32e"], out_f=p["f32a"], cap=16)
 
     def but(self, **changes):
         v = dict(self.v)
@@ -63,6 +63,9 @@ FAMILIES = {
     "crowding": ("rsasa_dot_crowding", True, "out_offsets", dict(n_bins=0),
                  lambda v: (v["n_points"], v["flags"], v["edges"], v["n_bins"], v["out_offsets"], v["out_a"], v["cap"],
                             v["out_b"], None)),
+    "enclosure": ("rsasa_dot_enclosure", True, "out_offsets", dict(n_dirs=0),
+                  lambda v: (v["n_points"], v["flags"], v["reach"], v["n_dirs"], v["out_offsets"], v["out_a"], v["cap"],
+                             v["out_b"], None)),
     "hse": ("rsasa_half_sphere_exposure", False, "out_a", dict(cutoff=-1.0),
             lambda v: (v["dirs"], v["flags"], v["cutoff"], v["out_a"], v["out_b"])),
     "within": ("rsasa_atoms_within", False, "out_offsets", dict(cutoff=-1.0),
@@ -115,6 +118,8 @@ def _pairs(family, batch):
         pairs.append(("a NULL output before the active indices", dict(active="active", n_active=2, **out), NULL))
     if family == "nearest":
         pairs.append(("k before cutoff", dict(k=0, cutoff=NAN), "k must be in [1, 256]"))
+    if family == "enclosure":
+        pairs.append(("n_dirs before reach", dict(n_dirs=0, reach=NAN), "n_dirs must be in [1, 32]"))
     if family == "radial":
         pairs.append(("n_classes before n_bins", dict(n_classes=0, n_bins=0), "n_classes must be in [1, 16]"))
         pairs.append(("edges before classes", dict(classes="high_class", edges="falling"), "edges must be non-decreasing"))
@@ -140,4 +145,4 @@ def test_every_family_and_form_is_covered():
     from rustsasa_amd import _capi
     stems = {FAMILIES[f][0] for f in FAMILIES}
     entry = {s for s in _capi.SYMBOLS if s in stems or (s.endswith("_batch") and s[:-6] in stems)}
-    assert len(FAMILIES) == 13 and len(entry) == 26
+    assert len(FAMILIES) == 14 and len(entry) == 28
