@@ -410,8 +410,10 @@ __global__ __launch_bounds__(64 * NW, NW >= 8 ? 6 : MX_MIN_WAVES)  /* 8 or 12 wa
         const float myR = mine.w + probe;
         const float my_sr = mine.w + g.max_r + 2.0f * probe;
         // ... and grids of at most 1024 cells per axis (the three cell coordinates share a register, below)
+        // (the largest of the three: their bitwise OR passes 1024 as soon as one axis has exactly 1024 cells and another has
+        // any, which left every atom of such a grid to the general kernel - tests/mx_cases.py range_dim_1024)
         ok_atoms = ballot64(myR >= 0.5f && my_sr <= 64.0f && probe >= 0.0f && probe <= 32.0f && (g.odd_radii & 1u) == 0u &&
-                            (g.dim_x | g.dim_y | g.dim_z) <= 1024u);
+                            max3u(g.dim_x, g.dim_y, g.dim_z) <= 1024u);
         if (lane < kWaveAtoms) {
             s_atom[w][lane] = kHoist ? make_float4(mine.x, mine.y, mine.z, myR) : mine;
             s_aux[w][lane] = make_uint2(kHoist ? __float_as_uint(my_sr * my_sr) : my_id32, __float_as_uint(1.0f / (2.0f * myR)));  // IEEE division: the correctly rounded reciprocal
