@@ -45,6 +45,8 @@ extern "C" {
  * RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS, rsasa_radial_counts, rsasa_radial_counts_batch;
  * rsasa_contact_owners, rsasa_contact_owners_batch; RSASA_CROWD_MAX_BINS, rsasa_dot_crowding,
  * rsasa_dot_crowding_batch; RSASA_ENCLOSE_MAX_DIRS, rsasa_dot_enclosure, rsasa_dot_enclosure_batch. */
+/* Additive under 4 as well: rsasa_dot_links, rsasa_dot_links_batch; rsasa_dot_geodesics, rsasa_dot_geodesics_batch;
+ * rsasa_context_geodesic_rounds. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -60,7 +62,8 @@ typedef enum rsasa_status {
                                         fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
                                         the same for its row buffers; rsasa_surface_components*: for out_labels;
                                         rsasa_dot_crowding*: for out_counts; rsasa_dot_enclosure*: for out_blocked;
-                                        rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries */
+                                        rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries;
+                                        rsasa_dot_links*: for out_link_offsets and out_entries */
 } rsasa_status;
 
 /* Mirrors `Atom` (reference src/structures/atomic.rs:13-24) without the
@@ -1055,6 +1058,186 @@ int rsasa_atoms_within_batch(rsasa_context_t *ctx,
                              const uint8_t *flags, float cutoff, int upper_only,
                              uint64_t *out_offsets,
                              rsasa_within_t *out_entries, size_t entries_capacity);
+
+/* ---- dot links ---------------------------------------------------------- */
+
+/* WHICH DOTS are next to a dot on the accessible surface: the graph that
+ * rsasa_surface_components labels, returned as per-dot lists in CSR form - the
+ * edge list of a graph network over the surface points, as rsasa_atoms_within
+ * is for atoms (declared here, behind rsasa_within_t, which its entries are).
+ *
+ * Definition.  Dots, their numbering, their positions q and the edge test are
+ * exactly those of rsasa_surface_components (see there: Dots, Place, Edges).
+ * The list of dot a holds every other dot b of its structure with float32
+ * d2 <= link * link.  Each entry is an rsasa_within_t: that d2, and idx = b's dot
+ * number within the structure.  Lists are ascending by the key
+ * (bits(d2) << 32) | idx, so the result compares byte for byte.  The test is
+ * symmetric: b is in a's list with the same d2 exactly when a is in b's.  A NaN
+ * dot has an empty list and is in nobody's.
+ *
+ *   out_dot_offsets   [n + 1], as rsasa_surface_components writes it; D is
+ *                     out_dot_offsets[n];
+ *   out_n_links       the total number of entries, written whenever
+ *                     out_dot_offsets is (0 if the call fails behind its
+ *                     argument rules before it has counted them);
+ *   out_link_offsets  [D + 1] (room for dots_capacity + 1): the list of the dot
+ *                     at array position d (batch-global, as out_labels is
+ *                     indexed) is out_entries[out_link_offsets[d] ..
+ *                     out_link_offsets[d + 1]); 64-bit, batch-global;
+ *   out_entries       [entries_capacity];
+ *   out_free[i]       (nullable) the popcount of rsasa_accessible_points;
+ *   out_sasa[i]       (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Sizing, in two calls: out_dot_offsets and *out_n_links are always written (on
+ * success and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_link_offsets or
+ * out_entries is NULL, dots_capacity < D or entries_capacity < *out_n_links,
+ * nothing else is written and RSASA_ERR_BUFFER_TOO_SMALL is returned: call once
+ * to size, allocate, call again - or pass generous buffers (a protein at 100
+ * points and the default link has about 6.4 dots per atom and 8.3 entries per
+ * dot).  The entries take 8 bytes each on the device as well (twice: in sweep
+ * order and sorted); a failed reservation returns RSASA_ERR_OUT_OF_MEMORY and
+ * the context stays usable.  Cost: the lists are ordered by one GPU lane per dot
+ * with L * L comparisons for a list of L entries - nothing at the 8 entries of a
+ * protein at the default link, but quadratic: a link that joins every dot of a
+ * sphere of tens of thousands of points to every other (lists of that length)
+ * keeps the device busy for seconds.
+ *
+ * link must be finite and >= 0, as for rsasa_surface_components; out_dot_offsets
+ * or out_n_links NULL returns RSASA_ERR_INVALID_ARGUMENT, and so does a batch
+ * with 2^31 - 1 or more dots.  The remaining argument errors and the non-finite
+ * input rules are those of rsasa_surface_components.  No atoms: RSASA_OK with
+ * out_dot_offsets[0] = 0, *out_n_links = 0 and (if given) out_link_offsets[0] = 0.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct). */
+int rsasa_dot_links(rsasa_context_t *ctx,
+                    const float *x, const float *y, const float *z, const float *radius,
+                    const uint64_t *id, size_t n_atoms,
+                    float probe_radius, size_t n_points, float link,
+                    uint64_t *out_dot_offsets, uint64_t *out_n_links,
+                    uint64_t *out_link_offsets, size_t dots_capacity,
+                    rsasa_within_t *out_entries, size_t entries_capacity,
+                    uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form, as rsasa_surface_components_batch: dots of different
+ * structures are never linked; out_dot_offsets and out_link_offsets are
+ * batch-global, idx is the dot number within the structure. */
+int rsasa_dot_links_batch(rsasa_context_t *ctx,
+                          const float *x, const float *y, const float *z, const float *radius,
+                          const uint64_t *id,
+                          const uint32_t *structure_offsets, size_t n_structures,
+                          float probe_radius, size_t n_points, float link,
+                          uint64_t *out_dot_offsets, uint64_t *out_n_links,
+                          uint64_t *out_link_offsets, size_t dots_capacity,
+                          rsasa_within_t *out_entries, size_t entries_capacity,
+                          uint32_t *out_free, float *out_atom_sasa);
+
+/* ---- dot geodesics ------------------------------------------------------ */
+
+/* HOW FAR ALONG THE SURFACE a dot lies from a set of seed dots: the shortest
+ * distance along the graph of rsasa_dot_links.  The dots within 12 A in space
+ * of a centre include the far wall of a cleft; the dots within 12 A along the
+ * surface do not (surface patches); seeded from the open dots of
+ * rsasa_dot_enclosure it is the depth of a pocket.
+ *
+ * Definition.  The graph is that of rsasa_dot_links at the same link.  seeds is
+ * one byte per accessible dot, in array order (the order of out_labels of
+ * rsasa_surface_components), nonzero = seed.  All arithmetic is float32 and
+ * unfused.
+ *
+ *   The edge weight is w(a, b) = sqrtf(d2), correctly rounded: the sqrt that
+ *   rsasa_atom_depth already exposes bit for bit.
+ *   The length of a path v0 ... vk is the left-to-right sum ((0 + w1) + w2) + ...
+ *   dist[v] is the minimum over all paths from any seed to v whose length, and
+ *   hence every prefix, is <= limit; +inf where there is none.  A seed has dist 0.
+ *
+ * Float addition of a non-negative number is monotone and never decreases its
+ * left operand.  So dist is also the unique least solution of
+ *
+ *     dist[v] = min(seed ? 0 : inf, min_u fl(dist[u] + w(u, v)))
+ *                                      with values > limit replaced by inf
+ *
+ * and any relaxation order, in place or double buffered, atomic or not,
+ * converges to these bits: (1) every value a relaxation ever stores is the
+ * length of a real path from a seed, so it is never below the least solution;
+ * (2) when no edge can lower anything the values solve the equation, and a
+ * solution reached from above through a monotone map is the least one.  The
+ * result can therefore be checked for equality, whatever the schedule of the GPU.
+ *
+ * out_source (nullable) is uint32: source[v] is the smallest seed dot number,
+ * within the structure, from which a path to v exists on which every vertex is
+ * reached at exactly its dist - the trivial path included, so a seed that
+ * coincides with a smaller seed has that one as its source.  It is 0xFFFFFFFF
+ * where dist is +inf.  Equivalently it is the least fixed point of
+ *
+ *     source[v] = min(seed ? v : none,
+ *                     min over u with fl(dist[u] + w(u, v)) == dist[v] of source[u])
+ *
+ * computed in a second phase over the converged dist (packed with dist into one
+ * 64-bit minimum it would depend on the schedule: two distances can round to the
+ * same sum).  Such a tight path exists for every finite dist.
+ *
+ *   out_dot_offsets  [n + 1], as rsasa_surface_components writes it; D is
+ *                    out_dot_offsets[n];
+ *   out_dist         [n_seed_bytes]: dist of the dot at each array position;
+ *   out_source       [n_seed_bytes] or NULL;
+ *   out_free[i]      (nullable) the popcount of rsasa_accessible_points;
+ *   out_sasa[i]      (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Sizing: the caller needs D to pass the seeds - from any earlier dot call on
+ * the same input (rsasa_surface_components, rsasa_dot_links, rsasa_dot_enclosure).
+ * out_dot_offsets is always written; if n_seed_bytes != D nothing else is and
+ * RSASA_ERR_INVALID_ARGUMENT is returned with a message (rsasa_context_last_error)
+ * that names both numbers.
+ *
+ * limit must be >= 0; +inf is allowed and means no limit (-0.0 is 0); NaN or a
+ * negative limit returns RSASA_ERR_INVALID_ARGUMENT.  link as for
+ * rsasa_dot_links, and so the bound of 2^31 - 1 dots, the remaining argument
+ * errors and the non-finite input rules: the dots of an atom with a NaN
+ * coordinate or radius have no edges - as seeds they have dist 0, otherwise
+ * +inf.  seeds or out_dist NULL with D > 0 returns RSASA_ERR_INVALID_ARGUMENT.
+ * No atoms: RSASA_OK with out_dot_offsets[0] = 0 (n_seed_bytes must be 0).  The
+ * lists stay on the device, 8 bytes per entry; a failed reservation returns
+ * RSASA_ERR_OUT_OF_MEMORY and the context stays usable.  A relaxation that has
+ * not settled after as many rounds as there are dots is a logic error and
+ * returns RSASA_ERR_INTERNAL.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct). */
+int rsasa_dot_geodesics(rsasa_context_t *ctx,
+                        const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms,
+                        float probe_radius, size_t n_points, float link,
+                        const uint8_t *seeds, size_t n_seed_bytes, float limit,
+                        uint64_t *out_dot_offsets,
+                        float *out_dist, uint32_t *out_source,
+                        uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form, as rsasa_dot_links_batch: no path crosses structures,
+ * all structures relax in the same launches; seeds, out_dist and out_source run
+ * over the dots of the whole batch, out_source holds dot numbers within the
+ * structure. */
+int rsasa_dot_geodesics_batch(rsasa_context_t *ctx,
+                              const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id,
+                              const uint32_t *structure_offsets, size_t n_structures,
+                              float probe_radius, size_t n_points, float link,
+                              const uint8_t *seeds, size_t n_seed_bytes, float limit,
+                              uint64_t *out_dot_offsets,
+                              float *out_dist, uint32_t *out_source,
+                              uint32_t *out_free, float *out_atom_sasa);
+
+/* A measurement, not part of any result: out_rounds[0 .. 2) get the rounds of
+ * relaxation that the context's last rsasa_dot_geodesics* call ran for dist and
+ * for source, the last round - which changed nothing - included; 0 / 0 before
+ * the first such call, after one that failed and for a phase that did not run.
+ * The counts depend on the GPU's schedule by a round or two; the results do
+ * not. */
+int rsasa_context_geodesic_rounds(rsasa_context_t *ctx, uint32_t *out_rounds);
 
 /* ---- the k nearest atoms ------------------------------------------------ */
 

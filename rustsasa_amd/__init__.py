@@ -7,7 +7,8 @@ library; the first call does, and raises if it is missing or no GPU is usable.
 from .engine import (ATOM_DTYPE, CROWD_MAX_BINS, CROWD_PARTNER, ENCLOSE_MAX_DIRS, ENCLOSE_PARTNER, HSE_CENTRE,
                      HSE_PARTNER, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_CENTRE, RADIAL_MAX_BINS, RADIAL_MAX_CLASSES,
                      RADIAL_PARTNER, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, Context, RsasaError, closest_pairs,
-                     component_table, contact_areas, default_link, device_count, dot_means, edge_index,
+                     component_table, contact_areas, default_link, device_count, dot_means, dot_seeds,
+                     dot_structure_offsets, edge_index,
                      enclosure_fraction, escape_vectors, group_areas, make_atoms, nearest_table, owner_areas,
                      pseudo_cb_directions, radial_density, residue_depth, sas_volume, sphere_points, split_sasa,
                      surface_points, unpack_points)
@@ -16,6 +17,6 @@ __all__ = ["ATOM_DTYPE", "CROWD_MAX_BINS", "CROWD_PARTNER", "ENCLOSE_MAX_DIRS", 
            "HSE_PARTNER", "NEAREST_MAX_K", "NEIGHBOR_DTYPE", "RADIAL_CENTRE", "RADIAL_MAX_BINS", "RADIAL_MAX_CLASSES",
            "RADIAL_PARTNER", "WITHIN_CENTRE", "WITHIN_DTYPE", "WITHIN_PARTNER", "Context", "RsasaError",
            "closest_pairs", "component_table", "contact_areas", "default_link", "device_count", "dot_means",
-           "edge_index", "enclosure_fraction", "escape_vectors", "group_areas", "make_atoms", "nearest_table",
-           "owner_areas", "pseudo_cb_directions", "radial_density", "residue_depth", "sas_volume", "sphere_points",
-           "split_sasa", "surface_points", "unpack_points"]
+           "dot_seeds", "dot_structure_offsets", "edge_index", "enclosure_fraction", "escape_vectors", "group_areas",
+           "make_atoms", "nearest_table", "owner_areas", "pseudo_cb_directions", "radial_density", "residue_depth",
+           "sas_volume", "sphere_points", "split_sasa", "surface_points", "unpack_points"]

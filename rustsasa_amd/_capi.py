@@ -148,6 +148,15 @@ SYMBOLS = {
                                      _vp, _vp, C.c_size_t]),
     "rsasa_atoms_within_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_float,
                                            C.c_int, _vp, _vp, C.c_size_t]),
+    "rsasa_dot_links": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, C.c_float, _vp, _vp, _vp,
+                                  C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_dot_links_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, C.c_float,
+                                        _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_dot_geodesics": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, C.c_float, _vp,
+                                      C.c_size_t, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "rsasa_dot_geodesics_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
+                                            C.c_float, _vp, C.c_size_t, C.c_float, _vp, _vp, _vp, _vp, _vp]),
+    "rsasa_context_geodesic_rounds": (C.c_int, [_vp, _vp]),
     "rsasa_nearest_atoms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_uint32, C.c_float,
                                       _vp, _vp, C.c_size_t]),
     "rsasa_nearest_atoms_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_uint32,

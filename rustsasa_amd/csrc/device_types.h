@@ -249,6 +249,27 @@ struct CcArgs {
     float link, link2;                  // two dots are linked when d2 <= link2 = link * link (one float32 product)
 };
 
+// ---- dot links and dot geodesics (geodesics.hip, rsasa_dot_links*, rsasa_dot_geodesics*) ----
+// The dots and the edge test of CcArgs (c.parent and c.labels unused): per dot the list of the dots linked to it, and the
+// shortest float32 path length along those lists from a set of seed dots.
+constexpr uint32_t kGdRounds = 8;       // rounds of the relaxation between two looks of the host at the flags
+struct GdArgs {
+    CcArgs c;                           // c.p.masks, c.free, c.dot_offsets, c.n_dots (here below 2^31), c.link, c.link2
+    uint32_t *counts;                   // [n_dots] the length of every dot's list (k_dot_link<kCount>; zeroed by the caller)
+    uint32_t *cursor;                   // [n_dots] the entries the fill pass accepted per dot (zeroed by the caller)
+    const unsigned long long *link_offsets;  // [n_dots + 1] exclusive scan of counts, batch-global
+    uint2 *raw;                         // [link_offsets[n_dots]] the lists in sweep order: (d2 bits, idx within the structure)
+                                        // for the links, (bits of sqrtf(d2), batch-wide dot) for the geodesics
+    uint2 *out;                         // links only: the lists ascending by (d2 bits << 32) | idx = rsasa_within_t
+    NbInfo *info;                       // mismatch: a cursor differs from its count
+    const uint8_t *seeds;               // geodesics: [n_dots], nonzero = seed
+    float limit;                        // a path longer than this is none (+inf: no limit)
+    uint32_t *dist;                     // [n_dots] float32 bits (all >= +0: they order like the numbers); +inf = unreached
+    uint32_t *stamp;                    // [n_dots] the last round in which the dot's value fell
+    uint32_t *source;                   // [n_dots] or null: the smallest seed (dot number within the structure) on a tight path
+    uint32_t *flags;                    // [kGdRounds] nonzero: that round of the current group lowered a value
+};
+
 // ---- dot crowding (crowding.hip, rsasa_dot_crowding*) ----
 // A finished point run (p.masks written, in input order), the grid it ran on and a flag byte per atom: the accessible
 // dots numbered as CcArgs numbers them and, per dot, the partner atoms of its structure by distance bin.
@@ -436,6 +457,14 @@ void launch_mask_free(const PtArgs &a, uint32_t *free, hipStream_t stream);
 void launch_atom_depth(const DpArgs &d, hipStream_t stream);
 // The component labels of the dots (components.hip) from those masks and counts, with CcArgs::dot_offsets.
 void launch_components(const CcArgs &c, hipStream_t stream);
+// The dot graph (geodesics.hip) from those masks and counts, with GdArgs::c.dot_offsets: the lists' lengths; then, with
+// link_offsets, the lists themselves (sorted, or as weights for the relaxation); the relaxation's start, its rounds
+// (kGdRounds per call, verdicts in GdArgs::flags) and the start of its source phase.
+void launch_dot_link_count(const GdArgs &gd, hipStream_t stream);
+void launch_dot_link_fill(const GdArgs &gd, bool weights, hipStream_t stream);
+void launch_geodesic_init(const GdArgs &gd, hipStream_t stream);
+void launch_geodesic_rounds(const GdArgs &gd, bool source, uint32_t first, hipStream_t stream);
+void launch_geodesic_restamp(const GdArgs &gd, hipStream_t stream);
 // The rows of the dots (crowding.hip) from those masks and counts, with DcArgs::dot_offsets and ::sorted_flags.
 void launch_dot_crowding(const DcArgs &d, hipStream_t stream);
 // The blocked directions of the dots (enclosure.hip) from those masks and counts, with DeArgs::dot_offsets and ::sorted_flags.

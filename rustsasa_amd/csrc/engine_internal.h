@@ -444,14 +444,15 @@ struct rsasa_context {
     size_t stream_sub_batches = 0; // a worker context of a stream of host batches: most sub-batches of a call (0: the default)
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
-    // The fourteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
-    // exposure vectors, atom depth, surface components, dot crowding, dot enclosure, contact counts, contact owners,
-    // group contacts; and
+    // The sixteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
+    // exposure vectors, atom depth, surface components, dot links, dot geodesics, dot crowding, dot enclosure, contact
+    // counts, contact owners, group contacts; and
     // the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest atoms, radial counts.  A
     // workspace of their own: device batches in flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls
     // queue their work on `stream` behind whatever it holds.  What outlives a call is here: the workspace's and the cell array's sizes, the pinned block the device's
     // verdicts come back in, and the lattice in the reference's order (the SASA path's cached lattices reorder the points
     // above 128) with the point count it holds (0: none).
+    uint32_t gd_rounds[2] = {0u, 0u};  // the rounds the context's last rsasa_dot_geodesics* call ran: dist, source (under mu)
     Workspace nb_ws;
     PinnedBlock nb_host;
     uint64_t nb_cell_capacity = 0;
@@ -481,6 +482,9 @@ struct rsasa_context {
         DeviceBuffer classes, so, table, pairs;
         DeviceBuffer crowd;  // dot crowding: a row of n_bins counts per dot (DcArgs::counts)
         DeviceBuffer enclose;  // dot enclosure: a word of blocked directions per dot (DeArgs::blocked)
+        // dot links and geodesics (GdArgs): per dot the counts, cursors and link offsets; per entry the lists in sweep order
+        // and sorted; per dot the seed bytes, dist, stamp and source; the rounds' flags
+        DeviceBuffer link_counts, link_cursor, link_offsets, link_raw, link_out, gd_seeds, gd_dist, gd_stamp, gd_source, gd_flags;
     } run;
 };
 

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 
 namespace rsasa {
 
@@ -80,6 +81,33 @@ inline const char *check_points(size_t N, const float *x, const float *y, const 
 inline const char *check_link(float link)
 {
     if (!(link >= 0.0f) || std::isinf(link)) return "link must be finite and not negative";
+    return nullptr;
+}
+
+// The limit of the dot geodesics: +inf (no limit) or finite, and not negative (-0.0 is 0).
+inline const char *check_geodesic_limit(float limit)
+{
+    if (!(limit >= 0.0f)) return "limit must be +inf or finite, and not negative";
+    return nullptr;
+}
+
+// The dots of the dot links and geodesics: their scan and their 32-bit round counter take fewer than 2^31 - 1.
+inline const char *check_dot_total(uint64_t n_dots)
+{
+    if (n_dots >= 0x7FFFFFFFull) return "2^31 - 1 or more accessible dots";
+    return nullptr;
+}
+
+// The seed bytes of the dot geodesics against the D dots the call found: one byte per dot, NULL only where D is 0.
+// why: room for the message that names both numbers (a caller who guessed reads D there).
+inline const char *check_seed_bytes(const uint8_t *seeds, size_t n_seed_bytes, uint64_t n_dots, char (&why)[96])
+{
+    if (n_seed_bytes != n_dots) {
+        std::snprintf(why, sizeof why, "n_seed_bytes is %llu but the structures have %llu accessible dots",
+                      (unsigned long long)n_seed_bytes, (unsigned long long)n_dots);
+        return why;
+    }
+    if (n_dots && !seeds) return "NULL argument";
     return nullptr;
 }
 

@@ -1,11 +1,12 @@
-// Host side of the fourteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
+// Host side of the sixteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
 // batch pair of include/rustsasa_amd.h: the neighbour lists (rsasa_precompute_neighbors*); the point runs built on
-// them - accessible points, exposure vectors, atom depth, surface components, dot crowding, dot enclosure, contact
-// counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
+// them - accessible points, exposure vectors, atom depth, surface components, dot links, dot geodesics, dot crowding,
+// dot enclosure, contact counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
 // atoms, radial counts.  The grid is built by the SASA path's kernels (nb_grid, and hs_grid for the runs on the grid
 // alone), then neighbors.hip counts, scans and fills the lists (nb_count, nb_fill).  A point run keeps the lists on the
 // device: every family shares one prologue (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and
-// adds its own kernels of points.hip, depth.hip, components.hip, crowding.hip or enclosure.hip and its own downloads.
+// adds its own kernels of points.hip, depth.hip, components.hip, geodesics.hip, crowding.hip or enclosure.hip and its
+// own downloads.
 // Every family is one function (*_run) behind its two entry points, which only forward to it: the single form as
 // Form::one(n_atoms), the batch form as Form::many(structure_offsets, n_structures).  The function opens with the rules
 // - entry_open: the context, N and the Cols (entry_checks.h: Cols::fix), n_points, the columns; then the family's own -
@@ -477,6 +478,177 @@ int cc_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     }
     RS_HIP(ctx, download(out_free, cc.free, c.N * 4, f.st));
     RS_HIP(ctx, download(out_sasa, cc.p.sasa, c.N * 4, f.st));
+    RS_HIP(ctx, hipStreamSynchronize(f.st));
+    return RSASA_OK;
+}
+
+// ---- dot links and dot geodesics (rsasa_dot_links*, rsasa_dot_geodesics*) ----
+
+// The opening both share, cc_run's: pt_run's masks stay on the device and become dot offsets (pt_dots), which the
+// caller gets; gd.c then describes the n_dots dots, under check_dot_total.
+int gd_dots(Run &f, const Cols &c, float probe, size_t n_points, float link, bool sasa, uint64_t *out_offsets, Lists &l,
+            GdArgs &gd, uint64_t &n_dots)
+{
+    int rc;
+    CcArgs &cc = gd.c;
+    if ((rc = pt_count(f, c, probe, nullptr, l)) || (rc = pt_prepare(f, l, n_points, true, sasa, cc.p)) ||
+        (rc = f.reserve(f.R.free, c.N * 4, cc.free)) || (rc = f.reserve(f.R.row_offsets, (c.N + 1) * 8, cc.dot_offsets)))
+        return rc;
+    cc.link = link;
+    cc.link2 = link * link;
+    if ((rc = pt_dots(f, l, cc.p, cc.free, nullptr, out_offsets, n_dots))) return rc;
+    RS_ARGS(f.ctx, check_dot_total(n_dots));
+    cc.n_dots = n_dots;
+    return RSASA_OK;
+}
+
+// The lengths of the lists of n_dots >= 1 dots and their offsets by the neighbour runs' scan (whose parts and info the
+// neighbour run has read); waits, and `total` is link_offsets[n_dots].  The cursors of the fill pass are zeroed too.
+int gd_count(Run &f, const Lists &l, GdArgs &gd, uint64_t &total)
+{
+    int rc;
+    const uint64_t n_dots = gd.c.n_dots;
+    NbArgs scan = l.a;
+    if ((rc = f.reserve(f.R.link_counts, n_dots * 4, gd.counts)) || (rc = f.reserve(f.R.link_cursor, n_dots * 4, gd.cursor)) ||
+        (rc = f.reserve(f.R.link_offsets, (n_dots + 1) * 8, scan.offsets)))
+        return rc;
+    RS_HIP(f.ctx, hipMemsetAsync(gd.counts, 0, n_dots * 4, f.st));
+    RS_HIP(f.ctx, hipMemsetAsync(gd.cursor, 0, n_dots * 4, f.st));
+    launch_dot_link_count(gd, f.st);
+    scan.b.n_atoms = (uint32_t)n_dots;  // (the scan's items are the dots)
+    scan.counts = gd.counts;
+    scan.stage = 0xFFFFFFFFu;  // (no list is long: the fill stages nothing)
+    launch_neighbor_scan(scan, f.st);
+    gd.link_offsets = scan.offsets;
+    gd.info = scan.info;
+    NbHost *h = static_cast<NbHost *>(f.ctx->nb_host.p);
+    RS_HIP(f.ctx, hipMemcpyAsync(&h->info, gd.info, sizeof(NbInfo), hipMemcpyDeviceToHost, f.st));
+    RS_HIP(f.ctx, hipGetLastError());
+    RS_HIP(f.ctx, hipStreamSynchronize(f.st));
+    total = h->info.total;
+    return RSASA_OK;
+}
+
+// One run of the dot links: the dots as in cc_run, the lists' lengths and offsets (gd_count); *out_n_links is written,
+// the caller's buffers are checked against the two totals, then k_dot_link fills and k_link_sort orders the lists.  8
+// bytes per atom, 8 per dot and 8 per entry come back (and 4 per atom each for the counts and the values, if asked).
+int dl_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id, Form form,
+           float probe, size_t n_points, float link, uint64_t *out_offsets, uint64_t *out_n_links, uint64_t *out_link_offsets,
+           size_t dots_cap, rsasa_within_t *out_entries, size_t cap, uint32_t *out_free, float *out_sasa)
+{
+    Cols c(x, y, z, r, id);
+    if (int rc = entry_open(ctx, c, form, &n_points, out_offsets && out_n_links, true)) return rc;
+    RS_ARGS(ctx, check_link(link));
+    *out_n_links = 0;  // (what a call that fails behind its rules leaves there, with or without the dot offsets)
+    Run f(ctx);
+    if (!f.open(c.N, out_offsets)) {
+        if (f.rc == RSASA_OK && out_link_offsets) out_link_offsets[0] = 0;  // (no atom: no dot, no entry)
+        return f.rc;
+    }
+    int rc;
+    Lists l;
+    GdArgs gd{};
+    uint64_t n_dots, total = 0;
+    if ((rc = gd_dots(f, c, probe, n_points, link, out_sasa != nullptr, out_offsets, l, gd, n_dots)) ||
+        (n_dots && (rc = gd_count(f, l, gd, total))))
+        return rc;
+    *out_n_links = total;
+    if (!out_link_offsets || dots_cap < n_dots || !out_entries || cap < total)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL,
+                    "out_link_offsets or out_entries is NULL or holds fewer dots than out_dot_offsets[n] or fewer entries than "
+                    "*out_n_links");
+    if (!n_dots) out_link_offsets[0] = 0;
+    if (total) {
+        if ((rc = f.reserve(f.R.link_raw, total * 8, gd.raw)) || (rc = f.reserve(f.R.link_out, total * 8, gd.out))) return rc;
+        launch_dot_link_fill(gd, false, f.st);
+        NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
+        RS_HIP(ctx, hipMemcpyAsync(&h->info, gd.info, sizeof(NbInfo), hipMemcpyDeviceToHost, f.st));
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, hipStreamSynchronize(f.st));
+        if (h->info.mismatch) return fail(ctx, RSASA_ERR_INTERNAL, "the fill pass of the dot links disagrees with its count pass");
+        RS_HIP(ctx, download(out_entries, gd.out, total * 8, f.st));
+    }
+    if (n_dots) RS_HIP(ctx, download(out_link_offsets, gd.link_offsets, (n_dots + 1) * 8, f.st));
+    RS_HIP(ctx, download(out_free, gd.c.free, c.N * 4, f.st));
+    RS_HIP(ctx, download(out_sasa, gd.c.p.sasa, c.N * 4, f.st));
+    RS_HIP(ctx, hipStreamSynchronize(f.st));
+    return RSASA_OK;
+}
+
+// One run of the dot geodesics: the dots and the lists' offsets as in dl_run, the seed bytes checked against the dots;
+// the lists are filled as weights and stay on the device unsorted, k_geo_init turns the seeds into dist, and the rounds
+// of k_geo_relax run kGdRounds at a time until one lowers nothing; then, if asked, the rounds of k_geo_source.  More
+// rounds than there are dots (and one) is RSASA_ERR_INTERNAL.  8 bytes per atom and 4 per dot come back (4 more per dot
+// for the sources, 4 per atom each for the counts and the values, if asked); the rounds run stay with the context
+// (rsasa_context::gd_rounds, rsasa_context_geodesic_rounds).
+int dg_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id, Form form,
+           float probe, size_t n_points, float link, const uint8_t *seeds, size_t n_seed_bytes, float limit,
+           uint64_t *out_offsets, float *out_dist, uint32_t *out_source, uint32_t *out_free, float *out_sasa)
+{
+    static_assert(sizeof(GdArgs) <= 4096, "kernel arguments");
+    Cols c(x, y, z, r, id);
+    if (int rc = entry_open(ctx, c, form, &n_points, out_offsets, true)) return rc;
+    RS_ARGS(ctx, check_link(link));
+    RS_ARGS(ctx, check_geodesic_limit(limit));
+    char why[96];
+    uint32_t n_rounds[2] = {0u, 0u};
+    Run f(ctx);
+    ctx->gd_rounds[0] = ctx->gd_rounds[1] = 0u;  // (under the mutex the frame holds)
+    if (!f.open(c.N, out_offsets)) {
+        if (f.rc == RSASA_OK) RS_ARGS(ctx, check_seed_bytes(seeds, n_seed_bytes, 0, why));
+        return f.rc;
+    }
+    int rc;
+    Lists l;
+    GdArgs gd{};
+    uint64_t n_dots, total = 0;
+    if ((rc = gd_dots(f, c, probe, n_points, link, out_sasa != nullptr, out_offsets, l, gd, n_dots))) return rc;
+    RS_ARGS(ctx, check_seed_bytes(seeds, n_seed_bytes, n_dots, why));
+    if (n_dots && !out_dist) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_dots) {
+        if ((rc = gd_count(f, l, gd, total)) || (total && (rc = f.reserve(f.R.link_raw, total * 8, gd.raw))) ||
+            (rc = f.upload(f.R.gd_seeds, seeds, n_dots, gd.seeds)) || (rc = f.reserve(f.R.gd_dist, n_dots * 4, gd.dist)) ||
+            (rc = f.reserve(f.R.gd_stamp, n_dots * 4, gd.stamp)) ||
+            (out_source && (rc = f.reserve(f.R.gd_source, n_dots * 4, gd.source))) ||
+            (rc = f.reserve(f.R.gd_flags, kGdRounds * 4, gd.flags)))
+            return rc;
+        gd.limit = limit + 0.0f;  // (-0.0 is 0)
+        if (total) launch_dot_link_fill(gd, true, f.st);
+        launch_geodesic_init(gd, f.st);
+        NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
+        // a phase: groups of kGdRounds rounds until one of them lowers nothing; n: the rounds run, that one included
+        auto phase = [&](bool source, uint32_t &n) -> int {
+            uint32_t flags[kGdRounds];
+            for (uint64_t first = 2;; first += kGdRounds) {
+                if (first > n_dots + 3)
+                    return fail(ctx, RSASA_ERR_INTERNAL, "the dot geodesics did not settle within as many rounds as there are dots");
+                RS_HIP(ctx, hipMemsetAsync(gd.flags, 0, sizeof flags, f.st));
+                launch_geodesic_rounds(gd, source, (uint32_t)first, f.st);
+                RS_HIP(ctx, hipMemcpyAsync(flags, gd.flags, sizeof flags, hipMemcpyDeviceToHost, f.st));
+                RS_HIP(ctx, hipMemcpyAsync(&h->info, gd.info, sizeof(NbInfo), hipMemcpyDeviceToHost, f.st));
+                RS_HIP(ctx, hipGetLastError());
+                RS_HIP(ctx, hipStreamSynchronize(f.st));
+                if (h->info.mismatch)
+                    return fail(ctx, RSASA_ERR_INTERNAL, "the fill pass of the dot links disagrees with its count pass");
+                for (uint32_t k = 0; k < kGdRounds; k++)
+                    if (!flags[k]) {
+                        n = (uint32_t)(first - 2) + k + 1u;
+                        return RSASA_OK;
+                    }
+            }
+        };
+        if ((rc = phase(false, n_rounds[0]))) return rc;
+        if (out_source) {
+            launch_geodesic_restamp(gd, f.st);
+            if ((rc = phase(true, n_rounds[1]))) return rc;
+        }
+        RS_HIP(ctx, download(out_dist, gd.dist, n_dots * 4, f.st));
+        RS_HIP(ctx, download(out_source, gd.source, n_dots * 4, f.st));
+    }
+    ctx->gd_rounds[0] = n_rounds[0];
+    ctx->gd_rounds[1] = n_rounds[1];
+    RS_HIP(ctx, download(out_free, gd.c.free, c.N * 4, f.st));
+    RS_HIP(ctx, download(out_sasa, gd.c.p.sasa, c.N * 4, f.st));
     RS_HIP(ctx, hipStreamSynchronize(f.st));
     return RSASA_OK;
 }
@@ -956,6 +1128,56 @@ int rsasa_surface_components_batch(rsasa_context_t *ctx, const float *x, const f
 {
     return cc_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, link,
                     out_dot_offsets, out_labels, labels_capacity, out_free, out_atom_sasa);
+}
+
+int rsasa_dot_links(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                    const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, float link,
+                    uint64_t *out_dot_offsets, uint64_t *out_n_links, uint64_t *out_link_offsets, size_t dots_capacity,
+                    rsasa_within_t *out_entries, size_t entries_capacity, uint32_t *out_free, float *out_sasa)
+{
+    return dl_run(ctx, x, y, z, radius, id, Form::one(n_atoms), probe_radius, n_points, link, out_dot_offsets, out_n_links,
+                    out_link_offsets, dots_capacity, out_entries, entries_capacity, out_free, out_sasa);
+}
+
+int rsasa_dot_links_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                          const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                          size_t n_points, float link, uint64_t *out_dot_offsets, uint64_t *out_n_links,
+                          uint64_t *out_link_offsets, size_t dots_capacity, rsasa_within_t *out_entries,
+                          size_t entries_capacity, uint32_t *out_free, float *out_atom_sasa)
+{
+    return dl_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, link,
+                    out_dot_offsets, out_n_links, out_link_offsets, dots_capacity, out_entries, entries_capacity, out_free,
+                    out_atom_sasa);
+}
+
+int rsasa_dot_geodesics(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, float link,
+                        const uint8_t *seeds, size_t n_seed_bytes, float limit, uint64_t *out_dot_offsets, float *out_dist,
+                        uint32_t *out_source, uint32_t *out_free, float *out_sasa)
+{
+    return dg_run(ctx, x, y, z, radius, id, Form::one(n_atoms), probe_radius, n_points, link, seeds, n_seed_bytes, limit,
+                    out_dot_offsets, out_dist, out_source, out_free, out_sasa);
+}
+
+int rsasa_dot_geodesics_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                              size_t n_points, float link, const uint8_t *seeds, size_t n_seed_bytes, float limit,
+                              uint64_t *out_dot_offsets, float *out_dist, uint32_t *out_source, uint32_t *out_free,
+                              float *out_atom_sasa)
+{
+    return dg_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, link, seeds,
+                    n_seed_bytes, limit, out_dot_offsets, out_dist, out_source, out_free, out_atom_sasa);
+}
+
+int rsasa_context_geodesic_rounds(rsasa_context_t *ctx, uint32_t *out_rounds)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!out_rounds) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "out_rounds is NULL");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    out_rounds[0] = ctx->gd_rounds[0];
+    out_rounds[1] = ctx->gd_rounds[1];
+    return RSASA_OK;
 }
 
 int rsasa_dot_crowding(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,

@@ -1,5 +1,5 @@
 // The shell sweep of the wave-per-atom kernels that search the grid beyond the neighbour reach (device only, gfx950
-// only): its frame (sh_frame), its driver (sh_sweep) and the steps the driver is made of.  Nine kernels sweep this way,
+// only): its frame (sh_frame), its driver (sh_sweep) and the steps the driver is made of.  Ten kernels sweep this way,
 // each with its own work per batch of atoms (the driver's `visit`) and its own stop rule (its `after`).
 // Run by sh_sweep:
 //   k_half_sphere (hse.hip)            sh_cutoff_reached(c2) of cutoff_sweep.h
@@ -11,12 +11,14 @@
 //                                      stopped by spheres of up to h around the atoms (written out it was not timed)
 // With the driver's three loops written out, because run by sh_sweep they measured slower on the MI355X at the same
 // registers, LDS and (within a few) instructions - the table is profiles/sweep_driver_ab.txt; their instruction streams
-// are the ones they had before the driver existed.  A change to sh_sweep is made in these three places too:
+// are the ones they had before the driver existed.  A change to sh_sweep is made in these four places too:
 //   wn_sweep of k_within_count and k_within_fill (within.hip)   sh_cutoff_reached(c2); the fill 1.1 to 1.2 % slower
 //   k_atom_depth (depth.hip)           best_d2 <= ((s - 2) h)^2, after reducing `best` over the wave; 3.6 to 4.7 % slower
 //   k_component_link (components.hip)  a fixed reach, shells 0 .. s_end, computed before the sweep; 9 % slower.  It does
 //                                      not take sh_frame either: with the frame alone its listing changes (936
 //                                      instructions for 932), and that build was not timed.
+//   k_dot_link (geodesics.hip)         k_component_link's loops and reach, copied with them: the three instantiations were
+//                                      never run through the driver, so the 9 % are the components kernel's, not theirs.
 // One wave per cell-sorted atom i.  The cells of its structure's grid are swept in Chebyshev shells s = 0, 1, 2, ... around
 // its own cell: shell s is the cells at distance exactly s, cut into x-runs of cell starts as nb_runs cuts the 5x5x5 block
 // - a row (y, z) on the rim of the shell's square gives the whole run [cx - s, cx + s], a row inside it the two cells
@@ -40,7 +42,7 @@
 // rounded sum of a radius and the probe), probe >= 0, and every |coordinate| <= 65536 h - a coordinate's ulp is at most
 // h / 128 and t' < 2^18, so t' is within 1/16 of the exact (x - min) / h, and |x_j - x_i| > (s - 1/8) h.  Every dot of j
 // lies within R_j <= h of c_j, and a dot q = c_j + R_j * s_k and a difference of two points carry a few roundings of at
-// most h / 128 each.  The stop rules of the nine kernels follow from this; without the margins every one of them sweeps
+// most h / 128 each.  The stop rules of the ten kernels follow from this; without the margins every one of them sweeps
 // until the shells cover the grid (ShCell::s_last), which is always exact.
 #pragma once
 #include "device_utils.h"

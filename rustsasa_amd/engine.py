@@ -391,6 +391,92 @@ class Context:
         the whole batch's radii."""
         return self._surface_components(x, y, z, radius, ids, probe_radius, n_points, link, structure_offsets)
 
+    # ---- dot links (the graph surface_components labels, as per-dot lists) ----
+    def _dot_links(self, x, y, z, radius, ids, probe_radius, n_points, link, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, _, _, radius, _), entry = self._entry("dot_links", x, y, z, radius, ids, structure_offsets)
+        link = default_link(radius, probe_radius, n_points) if link is None else link
+        n = x.shape[0]
+        free, sasa = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        dot_offsets, n_links = np.zeros(n + 1, np.uint64), np.zeros(1, np.uint64)
+        # the first guess: proteins have 4 to 7 accessible dots per atom at 100 points and 8.3 entries per dot at the
+        # default link; the second call is sized by what the first one wrote
+        dots_cap = min(n_points, 16) * n
+        cap = 12 * dots_cap
+        for _ in range(2):
+            link_offsets, entries = np.zeros(dots_cap + 1, np.uint64), np.empty(cap, WITHIN_DTYPE)
+            rc = entry(probe_radius, n_points, link, ptr(dot_offsets), ptr(n_links), ptr(link_offsets), dots_cap,
+                       ptr(entries), cap, ptr(free), ptr(sasa))
+            if rc != _capi.RSASA_ERR_BUFFER_TOO_SMALL:
+                break
+            dots_cap, cap = int(dot_offsets[-1]), int(n_links[0])
+        self._check(rc)
+        return dot_offsets, link_offsets[:int(dot_offsets[-1]) + 1], entries[:int(n_links[0])], free, sasa
+
+    def dot_links(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, link=None):
+        """rsasa_dot_links: (dot_offsets uint64[N + 1], link_offsets uint64[D + 1], entries WITHIN_DTYPE[total],
+        free uint32[N], sasa float32[N]).  Dots, numbering and the edge test are surface_components': the list of the dot
+        at position d, entries[link_offsets[d]:link_offsets[d + 1]], holds every other dot b of its structure with
+        float32 d2 <= link * link as (d2, idx = b's dot number within the structure), ascending by (d2, idx); the test
+        is symmetric.  link None: default_link(radius, probe_radius, n_points).
+        edge_index(link_offsets, entries, dot_structure_offsets(dot_offsets, structure_offsets)) gives the graph's
+        int64[2, E]."""
+        return self._dot_links(x, y, z, radius, ids, probe_radius, n_points, link)
+
+    def dot_links_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100,
+                        link=None):
+        """rsasa_dot_links_batch: dot_links of every structure (one grid each, dots of different structures are never
+        linked); dot_offsets and link_offsets run over the whole batch, idx is the dot number within the structure."""
+        return self._dot_links(x, y, z, radius, ids, probe_radius, n_points, link, structure_offsets)
+
+    # ---- dot geodesics (the shortest distance along that graph from a set of seed dots) ----
+    def _dot_geodesics(self, x, y, z, radius, ids, probe_radius, n_points, seeds, limit, link, sources,
+                       structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, _, _, radius, _), entry = self._entry("dot_geodesics", x, y, z, radius, ids, structure_offsets)
+        link = default_link(radius, probe_radius, n_points) if link is None else link
+        seeds = np.asarray(seeds)
+        if seeds.dtype.kind not in "uib" or seeds.ndim != 1:
+            raise ValueError("seeds must be a 1-D array of one byte per accessible dot (uint8, nonzero = seed)")
+        seeds = np.ascontiguousarray(seeds != 0, dtype=np.uint8)
+        limit = float("inf") if limit is None else float(limit)
+        if not limit >= 0.0:
+            raise ValueError("limit must be None (no limit), +inf or finite, and not negative")
+        n, d = x.shape[0], seeds.shape[0]
+        free, sasa = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        dot_offsets = np.zeros(n + 1, np.uint64)
+        dist = np.zeros(d, np.float32)
+        source = np.zeros(d, np.uint32) if sources else None
+        self._check(entry(probe_radius, n_points, link, ptr(seeds), d, limit, ptr(dot_offsets), ptr(dist), ptr(source),
+                          ptr(free), ptr(sasa)))
+        return (dot_offsets, dist, free, sasa) + ((source,) if sources else ())
+
+    def dot_geodesics(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, seeds=None,
+                      limit=None, link=None, sources: bool = False):
+        """rsasa_dot_geodesics: (dot_offsets uint64[N + 1], dist float32[D], free uint32[N], sasa float32[N]), and
+        source uint32[D] behind them with sources=True.  seeds: uint8[D], one byte per accessible dot in the order of
+        surface_points(), nonzero = seed (dot_seeds() marks all dots of given atoms); a wrong length raises with D in
+        the message.  dist[v] is the minimum over the paths of dot_links' graph from any seed to v of the float32
+        left-to-right sum of the edge weights sqrt(d2), over the paths no longer than `limit` (None: no limit); +inf
+        where there is none, 0 at a seed.  Any relaxation order converges to these bits, so they can be checked for
+        equality.  source[v] is the smallest seed dot number (within the structure) on a path that reaches every vertex
+        at exactly its dist, 0xFFFFFFFF where dist is +inf.  link None: default_link(radius, probe_radius, n_points)."""
+        return self._dot_geodesics(x, y, z, radius, ids, probe_radius, n_points, seeds, limit, link, sources)
+
+    def dot_geodesics_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100,
+                            seeds=None, limit=None, link=None, sources: bool = False):
+        """rsasa_dot_geodesics_batch: dot_geodesics of every structure (one grid each, no path crosses structures; all
+        structures relax in the same launches); seeds, dist and source run over the dots of the whole batch."""
+        return self._dot_geodesics(x, y, z, radius, ids, probe_radius, n_points, seeds, limit, link, sources,
+                                   structure_offsets)
+
+    def geodesic_rounds(self):
+        """rsasa_context_geodesic_rounds: (rounds for dist, rounds for source) of this context's last dot_geodesics[_batch]
+        call, the last round - which changed nothing - included.  A measurement: it varies with the GPU's schedule."""
+        rounds = np.zeros(2, np.uint32)
+        self._check(self._lib.rsasa_context_geodesic_rounds(self._h, ptr(rounds)))
+        return int(rounds[0]), int(rounds[1])
+
     # ---- dot crowding (how much protein lies around each accessible dot, by distance bin) ----
     def _dot_crowding(self, x, y, z, radius, ids, probe_radius, n_points, edges, flags, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -1048,6 +1134,43 @@ def default_link(radius, probe_radius: float = 1.4, n_points: int = 100) -> np.f
     return np.float32(1.5 * np.sqrt(4.0 * np.pi / n_points) * (max_r + float(probe_radius)))
 
 
+def _dot_offsets(dot_offsets):
+    off = np.ascontiguousarray(dot_offsets, dtype=np.uint64).astype(np.int64)
+    if off.ndim != 1 or off.shape[0] < 1 or off[0] != 0 or (np.diff(off) < 0).any():
+        raise ValueError("dot_offsets must be a 1-D array, non-decreasing from 0")
+    return off
+
+
+def dot_seeds(dot_offsets, atoms) -> np.ndarray:
+    """uint8[D]: the seed bytes of dot_geodesics[_batch] that mark all dots of the given atoms (batch-global atom
+    indices, or a boolean mask over the atoms); atom i's dots are [dot_offsets[i], dot_offsets[i + 1])."""
+    off = _dot_offsets(dot_offsets)
+    n = off.shape[0] - 1
+    atoms = np.asarray(atoms)
+    chosen = np.zeros(n, bool)
+    if atoms.dtype == bool:
+        if atoms.shape != (n,):
+            raise ValueError(f"a mask of atoms must have {n} entries")
+        chosen = atoms
+    else:
+        if atoms.size and (atoms.dtype.kind not in "ui" or int(atoms.min()) < 0 or int(atoms.max()) >= n):
+            raise ValueError(f"atoms must be integer indices in [0, {n})")
+        chosen[atoms.astype(np.int64).reshape(-1)] = True
+    return np.repeat(chosen, np.diff(off)).astype(np.uint8)
+
+
+def dot_structure_offsets(dot_offsets, structure_offsets=None) -> np.ndarray:
+    """int64[S + 1]: where every structure's dots begin in the batch-wide dot order, dot_offsets[structure_offsets] - the
+    structure_offsets to give edge_index() with the lists of dot_links[_batch].  None: one structure."""
+    off = _dot_offsets(dot_offsets)
+    if structure_offsets is None:
+        return np.array([0, off[-1]], np.int64)
+    so = _offsets("structure_offsets", structure_offsets).astype(np.int64)
+    if so[0] != 0 or so[-1] != off.shape[0] - 1 or (np.diff(so) < 0).any():
+        raise ValueError("structure_offsets must be non-decreasing from 0 to the number of atoms")
+    return off[so]
+
+
 def _dots(dot_offsets, labels, radius, probe_radius, n_points, structure_offsets):
     """The checked arguments of component_table / split_sasa: (dot offsets int64[N + 1], labels int64[D], structure
     offsets int64[S + 1], owner int64[D], dot area float64[D])."""
@@ -1231,4 +1354,5 @@ def make_atoms(x, y, z, radius, ids) -> np.ndarray:
 __all__ = ["Context", "RsasaError", "device_count", "sphere_points", "make_atoms", "unpack_points", "surface_points",
            "ENCLOSE_MAX_DIRS", "ENCLOSE_PARTNER", "enclosure_fraction", "escape_vectors",
            "contact_areas", "group_areas", "owner_areas", "sas_volume", "residue_depth", "default_link", "component_table", "split_sasa",
+           "dot_seeds", "dot_structure_offsets",
            "ATOM_DTYPE", "NEIGHBOR_DTYPE"]
