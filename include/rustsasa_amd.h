@@ -47,6 +47,7 @@ extern "C" {
  * rsasa_dot_crowding_batch; RSASA_ENCLOSE_MAX_DIRS, rsasa_dot_enclosure, rsasa_dot_enclosure_batch. */
 /* Additive under 4 as well: rsasa_dot_links, rsasa_dot_links_batch; rsasa_dot_geodesics, rsasa_dot_geodesics_batch;
  * rsasa_context_geodesic_rounds. */
+/* And: rsasa_dot_patches, rsasa_dot_patches_batch; rsasa_context_patch_stats. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -64,6 +65,7 @@ typedef enum rsasa_status {
                                         rsasa_dot_crowding*: for out_counts; rsasa_dot_enclosure*: for out_blocked;
                                         rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries;
                                         rsasa_dot_links*: for out_link_offsets and out_entries */
+                                     /* rsasa_dot_patches*: for its centre and dot buffers (see there) */
 } rsasa_status;
 
 /* Mirrors `Atom` (reference src/structures/atomic.rs:13-24) without the
@@ -1238,6 +1240,123 @@ int rsasa_dot_geodesics_batch(rsasa_context_t *ctx,
  * The counts depend on the GPU's schedule by a round or two; the results do
  * not. */
 int rsasa_context_geodesic_rounds(rsasa_context_t *ctx, uint32_t *out_rounds);
+
+/* ---- dot patches -------------------------------------------------------- */
+
+/* WHERE TO PUT THE PATCHES: a set of centre dots that covers the accessible
+ * surface evenly ALONG the surface - surface fingerprints, patch descriptors,
+ * coarse-grained interface maps, one representative per 6 A of pocket wall.
+ * Geodesic farthest-point sampling: repeatedly the dot farthest from the
+ * centres chosen so far becomes a centre, until no dot lies further than
+ * `spacing` from its nearest centre.  One call replaces a host loop of one
+ * rsasa_dot_geodesics_batch call per centre.
+ *
+ * Definition.  Graph, dots, numbering, weights and path length are those of
+ * rsasa_dot_geodesics at the same link; there is no limit.  Each structure,
+ * with D_s dots numbered within the structure, is sampled on its own:
+ *
+ *   dist_0[v] = +inf for every dot.
+ *   Before pick k let m = max_v dist_k[v].  Sampling stops when
+ *   k == min(max_centres, D_s), or D_s is 0, or m is finite and m <= spacing
+ *   (float32 compare).  A dot at +inf is therefore always picked, and
+ *   spacing = +inf gives exactly one centre per connected component.
+ *   Otherwise c_k is the dot with dist_k == m, the smallest dot number among
+ *   equals, and cover[k] = m (+inf for the first centre of a component).
+ *   dist_{k+1} is the rsasa_dot_geodesics solution with seeds {c_0 .. c_k} and
+ *   no limit.
+ *
+ * dist_{k+1} is computed from dist_k: with dist[c_k] = 0 every stored value is
+ * still the length of a real path from a seed, and a relaxation from there
+ * reaches the least solution for the larger seed set from above - the same bits
+ * as a relaxation from scratch (rsasa_dot_geodesics: why any order converges).
+ * So the results can be checked for equality, whatever the schedule of the GPU.
+ *
+ * Consequences: cover[k + 1] <= cover[k] as floats; the centres with cover ==
+ * +inf are exactly the distinct rsasa_surface_components labels of the structure,
+ * ascending, and they come first; unless max_centres cut the sampling short
+ * every dist <= spacing, and only then can a dot stay at +inf; any two centres
+ * are more than spacing apart along the graph; a dot without edges - every dot
+ * of an atom with a NaN coordinate or radius among them - is its own centre.
+ *
+ *   out_dot_offsets     [n + 1], as rsasa_surface_components writes it; D is
+ *                       out_dot_offsets[n].  Always written;
+ *   *out_centre_bound   B = sum over the structures of min(max_centres, D_s): the
+ *                       most centres the call can return.  Always written;
+ *   out_centre_offsets  [S + 1] (S = n_structures; [0, K] for one structure):
+ *                       structure s owns the centres [out_centre_offsets[s],
+ *                       out_centre_offsets[s + 1]); 64-bit, batch-global;
+ *   out_centres         [centres_capacity]: the centres in pick order, dot
+ *                       numbers within the structure;
+ *   out_cover           [centres_capacity]: cover of each centre;
+ *   out_dist            [dots_capacity]: the final dist of the dot at each array
+ *                       position;
+ *   out_source          [dots_capacity] or NULL: exactly rsasa_dot_geodesics'
+ *                       source for the seed set `centres` - the smallest centre
+ *                       dot number with a tight path, 0xFFFFFFFF where dist is
+ *                       +inf: the patch a dot belongs to;
+ *   out_free[i]         (nullable) the popcount of rsasa_accessible_points;
+ *   out_sasa[i]         (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Sizing, in two calls: if out_centre_offsets, out_centres, out_cover or
+ * out_dist is NULL, dots_capacity < D or centres_capacity < B, nothing beyond
+ * out_dot_offsets and *out_centre_bound is written, no sampling runs and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned: call once to size, allocate, call
+ * again.  A capacity of D always suffices for the centres.
+ *
+ * spacing must be finite and >= 0, or +inf (-0.0 is 0); NaN or a negative value
+ * returns RSASA_ERR_INVALID_ARGUMENT, and so does max_centres == 0 or
+ * out_dot_offsets or out_centre_bound NULL.  link, the bound of 2^31 - 1 dots,
+ * the remaining argument errors and the non-finite input rules are those of
+ * rsasa_dot_links.  No atoms: RSASA_OK with out_dot_offsets[0] = 0,
+ * *out_centre_bound = 0 and (if given) out_centre_offsets all 0.
+ *
+ * Cost.  One GPU workgroup samples one structure, all its picks in one launch:
+ * a pick reads the structure's D_s distances once (the argmax) and then relaxes
+ * only where the new centre lowers something, a frontier step at a time.  The
+ * structures of a batch run side by side; ONE large structure is sampled by one
+ * workgroup alone and takes as long as its picks times its dots.
+ * A sampler that leaves one of its bounded loops is a logic error and returns
+ * RSASA_ERR_INTERNAL.
+ *
+ * Synchronous, in the neighbour calls' workspace on the context's first
+ * stream: device batches in flight are neither waited for nor disturbed. */
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct). */
+int rsasa_dot_patches(rsasa_context_t *ctx,
+                      const float *x, const float *y, const float *z, const float *radius,
+                      const uint64_t *id, size_t n_atoms,
+                      float probe_radius, size_t n_points, float link,
+                      float spacing, uint32_t max_centres,
+                      uint64_t *out_dot_offsets, uint64_t *out_centre_bound,
+                      uint64_t *out_centre_offsets,
+                      uint32_t *out_centres, float *out_cover, size_t centres_capacity,
+                      float *out_dist, uint32_t *out_source, size_t dots_capacity,
+                      uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form, as rsasa_dot_geodesics_batch: every structure is sampled
+ * on its own, all of them in the same launch; out_dist and out_source run over
+ * the dots of the whole batch, out_centres and out_source hold dot numbers
+ * within the structure. */
+int rsasa_dot_patches_batch(rsasa_context_t *ctx,
+                            const float *x, const float *y, const float *z, const float *radius,
+                            const uint64_t *id,
+                            const uint32_t *structure_offsets, size_t n_structures,
+                            float probe_radius, size_t n_points, float link,
+                            float spacing, uint32_t max_centres,
+                            uint64_t *out_dot_offsets, uint64_t *out_centre_bound,
+                            uint64_t *out_centre_offsets,
+                            uint32_t *out_centres, float *out_cover, size_t centres_capacity,
+                            float *out_dist, uint32_t *out_source, size_t dots_capacity,
+                            uint32_t *out_free, float *out_atom_sasa);
+
+/* A measurement, not part of any result: out_stats[0 .. 3) get, for the
+ * context's last rsasa_dot_patches* call, the picks (the centres returned), the
+ * relaxation steps summed over the structures - the step of each pick that
+ * lowered nothing included - and the picks whose frontier outgrew the sampler's
+ * queue and finished on the slower scan.  0 / 0 / 0 before the first such call
+ * and after one that failed or only sized.  The steps and overflows depend on
+ * the GPU's schedule; the results do not. */
+int rsasa_context_patch_stats(rsasa_context_t *ctx, uint64_t *out_stats);
 
 /* ---- the k nearest atoms ------------------------------------------------ */
 

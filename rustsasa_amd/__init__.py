@@ -8,15 +8,15 @@ from .engine import (ATOM_DTYPE, CROWD_MAX_BINS, CROWD_PARTNER, ENCLOSE_MAX_DIRS
                      HSE_PARTNER, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_CENTRE, RADIAL_MAX_BINS, RADIAL_MAX_CLASSES,
                      RADIAL_PARTNER, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, Context, RsasaError, closest_pairs,
                      component_table, contact_areas, default_link, device_count, dot_means, dot_seeds,
-                     dot_structure_offsets, edge_index,
+                     dot_seeds_from, dot_structure_offsets, edge_index,
                      enclosure_fraction, escape_vectors, group_areas, make_atoms, nearest_table, owner_areas,
-                     pseudo_cb_directions, radial_density, residue_depth, sas_volume, sphere_points, split_sasa,
+                     patch_index, patch_table, pseudo_cb_directions, radial_density, residue_depth, sas_volume, sphere_points, split_sasa,
                      surface_points, unpack_points)
 
 __all__ = ["ATOM_DTYPE", "CROWD_MAX_BINS", "CROWD_PARTNER", "ENCLOSE_MAX_DIRS", "ENCLOSE_PARTNER", "HSE_CENTRE",
            "HSE_PARTNER", "NEAREST_MAX_K", "NEIGHBOR_DTYPE", "RADIAL_CENTRE", "RADIAL_MAX_BINS", "RADIAL_MAX_CLASSES",
            "RADIAL_PARTNER", "WITHIN_CENTRE", "WITHIN_DTYPE", "WITHIN_PARTNER", "Context", "RsasaError",
            "closest_pairs", "component_table", "contact_areas", "default_link", "device_count", "dot_means",
-           "dot_seeds", "dot_structure_offsets", "edge_index", "enclosure_fraction", "escape_vectors", "group_areas",
-           "make_atoms", "nearest_table", "owner_areas", "pseudo_cb_directions", "radial_density", "residue_depth",
+           "dot_seeds", "dot_seeds_from", "dot_structure_offsets", "edge_index", "enclosure_fraction", "escape_vectors", "group_areas",
+           "make_atoms", "nearest_table", "owner_areas", "patch_index", "patch_table", "pseudo_cb_directions", "radial_density", "residue_depth",
            "sas_volume", "sphere_points", "split_sasa", "surface_points", "unpack_points"]

@@ -157,6 +157,12 @@ SYMBOLS = {
     "rsasa_dot_geodesics_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t,
                                             C.c_float, _vp, C.c_size_t, C.c_float, _vp, _vp, _vp, _vp, _vp]),
     "rsasa_context_geodesic_rounds": (C.c_int, [_vp, _vp]),
+    "rsasa_dot_patches": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, C.c_float, C.c_float,
+                                    C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_dot_patches_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, C.c_float,
+                                          C.c_float, C.c_uint32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_size_t,
+                                          _vp, _vp]),
+    "rsasa_context_patch_stats": (C.c_int, [_vp, _vp]),
     "rsasa_nearest_atoms": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_uint32, C.c_float,
                                       _vp, _vp, C.c_size_t]),
     "rsasa_nearest_atoms_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, _vp, C.c_uint32,

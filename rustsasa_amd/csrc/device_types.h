@@ -270,6 +270,31 @@ struct GdArgs {
     uint32_t *flags;                    // [kGdRounds] nonzero: that round of the current group lowered a value
 };
 
+// ---- dot patches (patches.hip, rsasa_dot_patches*) ----
+// The lists of the geodesics (g.raw as weights) and their dist, stamp and source: per structure the farthest-point
+// sample of its dots along the graph, one workgroup of k_patch_sample per structure.
+constexpr uint32_t kPsBlock = 256;      // lanes of a k_patch_sample workgroup
+constexpr uint32_t kPsQueue = 1024;     // dots a frontier queue in LDS holds; a longer frontier falls back to the stamp scan
+struct PsStats {                        // what k_patch_sample adds up over the structures of a call
+    unsigned long long picks, steps, overflows;
+    unsigned long long error;           // nonzero: a structure left one of its bounded loops (a logic error)
+};
+struct PsArgs {
+    GdArgs g;                           // g.c (dots), g.link_offsets, g.raw, g.cursor, g.info, g.dist, g.stamp, g.source (nullable)
+    const uint32_t *so;                 // [n_structures + 1] the structures' offsets in input order
+    uint32_t n_structures;
+    float spacing;                      // sampling stops when the farthest dot is finite and <= spacing (+inf: one centre a component)
+    uint32_t max_centres;               // >= 1
+    const unsigned long long *slot_offsets;  // [n_structures + 1] exclusive scan of min(max_centres, D_s): a structure's room
+    uint32_t *centres;                  // [slot_offsets[n_structures]] the centres in pick order, dot numbers within the structure
+    uint32_t *cover;                    // the same room: float32 bits of the farthest distance before each pick
+    uint32_t *n_centres;                // [n_structures] the picks of each structure
+    PsStats *stats;                     // zeroed by the caller
+    // k_patch_pack, once the host has scanned n_centres: the centres and covers without the unused room between structures
+    const unsigned long long *centre_offsets;  // [n_structures + 1] exclusive scan of n_centres
+    uint32_t *packed_centres, *packed_cover;    // [centre_offsets[n_structures]]
+};
+
 // ---- dot crowding (crowding.hip, rsasa_dot_crowding*) ----
 // A finished point run (p.masks written, in input order), the grid it ran on and a flag byte per atom: the accessible
 // dots numbered as CcArgs numbers them and, per dot, the partner atoms of its structure by distance bin.
@@ -465,6 +490,11 @@ void launch_dot_link_fill(const GdArgs &gd, bool weights, hipStream_t stream);
 void launch_geodesic_init(const GdArgs &gd, hipStream_t stream);
 void launch_geodesic_rounds(const GdArgs &gd, bool source, uint32_t first, hipStream_t stream);
 void launch_geodesic_restamp(const GdArgs &gd, hipStream_t stream);
+// The farthest-point sample (patches.hip) on the weighted lists of the geodesics: dist, stamp and source cleared (and the
+// fill's cursors checked), then every structure's picks in one launch.
+void launch_patch_sample(const PsArgs &ps, hipStream_t stream);
+// The centres and covers of the sample moved together (patches.hip): ps.centre_offsets -> ps.packed_centres, ps.packed_cover.
+void launch_patch_pack(const PsArgs &ps, hipStream_t stream);
 // The rows of the dots (crowding.hip) from those masks and counts, with DcArgs::dot_offsets and ::sorted_flags.
 void launch_dot_crowding(const DcArgs &d, hipStream_t stream);
 // The blocked directions of the dots (enclosure.hip) from those masks and counts, with DeArgs::dot_offsets and ::sorted_flags.

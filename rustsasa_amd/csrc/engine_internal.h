@@ -444,8 +444,8 @@ struct rsasa_context {
     size_t stream_sub_batches = 0; // a worker context of a stream of host batches: most sub-batches of a call (0: the default)
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
-    // The sixteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
-    // exposure vectors, atom depth, surface components, dot links, dot geodesics, dot crowding, dot enclosure, contact
+    // The seventeen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
+    // exposure vectors, atom depth, surface components, dot links, dot geodesics, dot patches, dot crowding, dot enclosure, contact
     // counts, contact owners, group contacts; and
     // the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest atoms, radial counts.  A
     // workspace of their own: device batches in flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls
@@ -453,6 +453,7 @@ struct rsasa_context {
     // verdicts come back in, and the lattice in the reference's order (the SASA path's cached lattices reorder the points
     // above 128) with the point count it holds (0: none).
     uint32_t gd_rounds[2] = {0u, 0u};  // the rounds the context's last rsasa_dot_geodesics* call ran: dist, source (under mu)
+    uint64_t ps_stats[3] = {0u, 0u, 0u};  // the picks, relaxation steps and queue overflows of the last rsasa_dot_patches* call (under mu)
     Workspace nb_ws;
     PinnedBlock nb_host;
     uint64_t nb_cell_capacity = 0;
@@ -485,6 +486,9 @@ struct rsasa_context {
         // dot links and geodesics (GdArgs): per dot the counts, cursors and link offsets; per entry the lists in sweep order
         // and sorted; per dot the seed bytes, dist, stamp and source; the rounds' flags
         DeviceBuffer link_counts, link_cursor, link_offsets, link_raw, link_out, gd_seeds, gd_dist, gd_stamp, gd_source, gd_flags;
+        // dot patches (PsArgs): per structure the room of its centres and their number; per slot of that room the centre and
+        // its cover; the sums of the sampler; the scan of the numbers and the centres and covers packed by it
+        DeviceBuffer ps_slots, ps_counts, ps_centres, ps_cover, ps_stats, ps_offsets, ps_packed;
     } run;
 };
 

@@ -111,6 +111,46 @@ inline const char *check_seed_bytes(const uint8_t *seeds, size_t n_seed_bytes, u
     return nullptr;
 }
 
+// The spacing of the dot patches: +inf (one centre per component) or finite, and not negative (-0.0 is 0).
+inline const char *check_patch_spacing(float spacing)
+{
+    if (!(spacing >= 0.0f)) return "spacing must be +inf or finite, and not negative";
+    return nullptr;
+}
+
+// The most centres a structure of the dot patches gets: at least one.
+inline const char *check_patch_max_centres(uint32_t max_centres)
+{
+    if (max_centres < 1u) return "max_centres must be at least 1";
+    return nullptr;
+}
+
+// The room the centres of the dot patches can take: slots[s] (S + 1 entries, nullable) becomes the exclusive scan of
+// min(max_centres, D_s) over the S structures, D_s being the dots of structure s - dot_offsets (N + 1 entries) at its
+// first atom so[s] and behind its last; returns the total B.
+inline uint64_t patch_centre_bound(const uint64_t *dot_offsets, const uint32_t *so, size_t S, uint32_t max_centres, uint64_t *slots)
+{
+    uint64_t B = 0;
+    for (size_t s = 0; s < S; s++) {
+        if (slots) slots[s] = B;
+        const uint64_t D = dot_offsets[so[s + 1]] - dot_offsets[so[s]];
+        B += D < max_centres ? D : (uint64_t)max_centres;
+    }
+    if (slots) slots[S] = B;
+    return B;
+}
+
+// The caller's buffers of the dot patches against the D dots and the bound B the call found: all four are needed, with
+// room for D dots and B centres.  The message stands for RSASA_ERR_BUFFER_TOO_SMALL.
+inline const char *check_patch_room(const void *centre_offsets, const void *centres, const void *cover, const void *dist,
+                                    size_t dots_capacity, uint64_t D, size_t centres_capacity, uint64_t B)
+{
+    if (!centre_offsets || !centres || !cover || !dist) return "out_centre_offsets, out_centres, out_cover or out_dist is NULL";
+    if (dots_capacity < D) return "out_dist holds fewer dots than out_dot_offsets[n]";
+    if (centres_capacity < B) return "out_centres and out_cover hold fewer centres than *out_centre_bound";
+    return nullptr;
+}
+
 // The cutoff of the half-sphere exposure: finite and not negative (-0.0 is 0).
 inline const char *check_cutoff(float cutoff)
 {

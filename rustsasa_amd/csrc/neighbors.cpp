@@ -1,11 +1,11 @@
-// Host side of the sixteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
+// Host side of the seventeen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
 // batch pair of include/rustsasa_amd.h: the neighbour lists (rsasa_precompute_neighbors*); the point runs built on
-// them - accessible points, exposure vectors, atom depth, surface components, dot links, dot geodesics, dot crowding,
+// them - accessible points, exposure vectors, atom depth, surface components, dot links, dot geodesics, dot patches, dot crowding,
 // dot enclosure, contact counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
 // atoms, radial counts.  The grid is built by the SASA path's kernels (nb_grid, and hs_grid for the runs on the grid
 // alone), then neighbors.hip counts, scans and fills the lists (nb_count, nb_fill).  A point run keeps the lists on the
 // device: every family shares one prologue (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and
-// adds its own kernels of points.hip, depth.hip, components.hip, geodesics.hip, crowding.hip or enclosure.hip and its
+// adds its own kernels of points.hip, depth.hip, components.hip, geodesics.hip, patches.hip, crowding.hip or enclosure.hip and its
 // own downloads.
 // Every family is one function (*_run) behind its two entry points, which only forward to it: the single form as
 // Form::one(n_atoms), the batch form as Form::many(structure_offsets, n_structures).  The function opens with the rules
@@ -575,6 +575,33 @@ int dl_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     return RSASA_OK;
 }
 
+// A phase of the geodesics over gd's n_dots >= 1 dots, whose start is queued: groups of kGdRounds rounds of the
+// relaxation (source false) or of the source phase until one of them lowers nothing; n: the rounds run, that one
+// included.  More rounds than there are dots (and one) is RSASA_ERR_INTERNAL.
+int gd_phase(Run &f, const GdArgs &gd, bool source, uint32_t &n)
+{
+    rsasa_context *ctx = f.ctx;
+    NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
+    uint32_t flags[kGdRounds];
+    for (uint64_t first = 2;; first += kGdRounds) {
+        if (first > gd.c.n_dots + 3)
+            return fail(ctx, RSASA_ERR_INTERNAL, "the dot geodesics did not settle within as many rounds as there are dots");
+        RS_HIP(ctx, hipMemsetAsync(gd.flags, 0, sizeof flags, f.st));
+        launch_geodesic_rounds(gd, source, (uint32_t)first, f.st);
+        RS_HIP(ctx, hipMemcpyAsync(flags, gd.flags, sizeof flags, hipMemcpyDeviceToHost, f.st));
+        RS_HIP(ctx, hipMemcpyAsync(&h->info, gd.info, sizeof(NbInfo), hipMemcpyDeviceToHost, f.st));
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, hipStreamSynchronize(f.st));
+        if (h->info.mismatch)
+            return fail(ctx, RSASA_ERR_INTERNAL, "the fill pass of the dot links disagrees with its count pass");
+        for (uint32_t k = 0; k < kGdRounds; k++)
+            if (!flags[k]) {
+                n = (uint32_t)(first - 2) + k + 1u;
+                return RSASA_OK;
+            }
+    }
+}
+
 // One run of the dot geodesics: the dots and the lists' offsets as in dl_run, the seed bytes checked against the dots;
 // the lists are filled as weights and stay on the device unsorted, k_geo_init turns the seeds into dist, and the rounds
 // of k_geo_relax run kGdRounds at a time until one lowers nothing; then, if asked, the rounds of k_geo_source.  More
@@ -615,32 +642,10 @@ int dg_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
         gd.limit = limit + 0.0f;  // (-0.0 is 0)
         if (total) launch_dot_link_fill(gd, true, f.st);
         launch_geodesic_init(gd, f.st);
-        NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
-        // a phase: groups of kGdRounds rounds until one of them lowers nothing; n: the rounds run, that one included
-        auto phase = [&](bool source, uint32_t &n) -> int {
-            uint32_t flags[kGdRounds];
-            for (uint64_t first = 2;; first += kGdRounds) {
-                if (first > n_dots + 3)
-                    return fail(ctx, RSASA_ERR_INTERNAL, "the dot geodesics did not settle within as many rounds as there are dots");
-                RS_HIP(ctx, hipMemsetAsync(gd.flags, 0, sizeof flags, f.st));
-                launch_geodesic_rounds(gd, source, (uint32_t)first, f.st);
-                RS_HIP(ctx, hipMemcpyAsync(flags, gd.flags, sizeof flags, hipMemcpyDeviceToHost, f.st));
-                RS_HIP(ctx, hipMemcpyAsync(&h->info, gd.info, sizeof(NbInfo), hipMemcpyDeviceToHost, f.st));
-                RS_HIP(ctx, hipGetLastError());
-                RS_HIP(ctx, hipStreamSynchronize(f.st));
-                if (h->info.mismatch)
-                    return fail(ctx, RSASA_ERR_INTERNAL, "the fill pass of the dot links disagrees with its count pass");
-                for (uint32_t k = 0; k < kGdRounds; k++)
-                    if (!flags[k]) {
-                        n = (uint32_t)(first - 2) + k + 1u;
-                        return RSASA_OK;
-                    }
-            }
-        };
-        if ((rc = phase(false, n_rounds[0]))) return rc;
+        if ((rc = gd_phase(f, gd, false, n_rounds[0]))) return rc;
         if (out_source) {
             launch_geodesic_restamp(gd, f.st);
-            if ((rc = phase(true, n_rounds[1]))) return rc;
+            if ((rc = gd_phase(f, gd, true, n_rounds[1]))) return rc;
         }
         RS_HIP(ctx, download(out_dist, gd.dist, n_dots * 4, f.st));
         RS_HIP(ctx, download(out_source, gd.source, n_dots * 4, f.st));
@@ -650,6 +655,106 @@ int dg_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     RS_HIP(ctx, download(out_free, gd.c.free, c.N * 4, f.st));
     RS_HIP(ctx, download(out_sasa, gd.c.p.sasa, c.N * 4, f.st));
     RS_HIP(ctx, hipStreamSynchronize(f.st));
+    return RSASA_OK;
+}
+
+// ---- dot patches (rsasa_dot_patches*) ----
+
+// One run of the dot patches: the dots and the weighted lists as in dg_run; *out_bound and the caller's buffers are
+// checked against the dots (check_patch_room) before anything is sampled.  k_patch_sample then makes every structure's
+// picks in one launch - one wait, no polling - and, if asked, the source phase of the geodesics runs from the centres it
+// marked.  The centres are packed on the device (k_patch_pack) once the host has scanned their counts.  8 bytes per atom, 4
+// per dot, 4 per structure and 8 per centre come back (4 more per dot for the sources, 4 per atom each for the counts and the values, if asked);
+// the sampler's sums stay with the context (rsasa_context::ps_stats, rsasa_context_patch_stats).
+int ps_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id, Form form,
+           float probe, size_t n_points, float link, float spacing, uint32_t max_centres, uint64_t *out_offsets,
+           uint64_t *out_bound, uint64_t *out_centre_offsets, uint32_t *out_centres, float *out_cover, size_t centres_cap,
+           float *out_dist, uint32_t *out_source, size_t dots_cap, uint32_t *out_free, float *out_sasa)
+{
+    static_assert(sizeof(PsArgs) <= 4096, "kernel arguments");
+    Cols c(x, y, z, r, id);
+    if (int rc = entry_open(ctx, c, form, &n_points, out_offsets && out_bound, true)) return rc;
+    RS_ARGS(ctx, check_link(link));
+    RS_ARGS(ctx, check_patch_spacing(spacing));
+    RS_ARGS(ctx, check_patch_max_centres(max_centres));
+    *out_bound = 0;
+    Run f(ctx);
+    ctx->ps_stats[0] = ctx->ps_stats[1] = ctx->ps_stats[2] = 0u;  // (under the mutex the frame holds)
+    if (!f.open(c.N, out_offsets)) {
+        if (f.rc == RSASA_OK && out_centre_offsets) std::fill(out_centre_offsets, out_centre_offsets + c.S + 1, 0ull);  // (no atom: no centre)
+        return f.rc;
+    }
+    int rc;
+    Lists l;
+    PsArgs ps{};
+    GdArgs &gd = ps.g;
+    uint64_t n_dots, total = 0;
+    if ((rc = gd_dots(f, c, probe, n_points, link, out_sasa != nullptr, out_offsets, l, gd, n_dots))) return rc;
+    std::vector<uint64_t> slots(c.S + 1);
+    const uint64_t bound = patch_centre_bound(out_offsets, c.so, c.S, max_centres, slots.data());
+    *out_bound = bound;
+    if (const char *msg = check_patch_room(out_centre_offsets, out_centres, out_cover, out_dist, dots_cap, n_dots, centres_cap, bound))
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, msg);
+    std::fill(out_centre_offsets, out_centre_offsets + c.S + 1, 0ull);
+    PsStats stats{};
+    if (n_dots) {
+        const unsigned long long *slot_offsets;
+        if ((rc = gd_count(f, l, gd, total)) || (total && (rc = f.reserve(f.R.link_raw, total * 8, gd.raw))) ||
+            (rc = f.reserve(f.R.gd_dist, n_dots * 4, gd.dist)) || (rc = f.reserve(f.R.gd_stamp, n_dots * 4, gd.stamp)) ||
+            (out_source && (rc = f.reserve(f.R.gd_source, n_dots * 4, gd.source))) ||
+            (rc = f.reserve(f.R.gd_flags, kGdRounds * 4, gd.flags)) || (rc = f.upload(f.R.so, c.so, (c.S + 1) * 4, ps.so)) ||
+            (rc = f.upload(f.R.ps_slots, (const unsigned long long *)slots.data(), (c.S + 1) * 8, slot_offsets)) ||
+            (rc = f.reserve(f.R.ps_counts, c.S * 4, ps.n_centres)) || (rc = f.reserve(f.R.ps_centres, bound * 4, ps.centres)) ||
+            (rc = f.reserve(f.R.ps_cover, bound * 4, ps.cover)) || (rc = f.reserve(f.R.ps_stats, sizeof(PsStats), ps.stats)))
+            return rc;
+        ps.slot_offsets = slot_offsets;
+        ps.n_structures = (uint32_t)c.S;
+        ps.spacing = spacing + 0.0f;  // (-0.0 is 0)
+        ps.max_centres = max_centres;
+        gd.limit = __builtin_inff();
+        RS_HIP(ctx, hipMemsetAsync(ps.stats, 0, sizeof(PsStats), f.st));
+        if (total) launch_dot_link_fill(gd, true, f.st);
+        launch_patch_sample(ps, f.st);
+        NbHost *h = static_cast<NbHost *>(ctx->nb_host.p);
+        std::vector<uint32_t> counts(c.S);
+        RS_HIP(ctx, hipMemcpyAsync(&stats, ps.stats, sizeof(PsStats), hipMemcpyDeviceToHost, f.st));
+        RS_HIP(ctx, hipMemcpyAsync(&h->info, gd.info, sizeof(NbInfo), hipMemcpyDeviceToHost, f.st));
+        RS_HIP(ctx, hipMemcpyAsync(counts.data(), ps.n_centres, c.S * 4, hipMemcpyDeviceToHost, f.st));
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, hipStreamSynchronize(f.st));
+        if (h->info.mismatch) return fail(ctx, RSASA_ERR_INTERNAL, "the fill pass of the dot links disagrees with its count pass");
+        if (stats.error) return fail(ctx, RSASA_ERR_INTERNAL, "the dot patches of a structure left a bounded loop of the sampler");
+        for (size_t s = 0; s < c.S; s++) {
+            if (counts[s] > slots[s + 1] - slots[s])
+                return fail(ctx, RSASA_ERR_INTERNAL, "a structure of the dot patches has more centres than its bound");
+            out_centre_offsets[s + 1] = out_centre_offsets[s] + counts[s];
+        }
+        // the centres without the unused room of the bound: K entries come back, packed on the device
+        const uint64_t n_centres = out_centre_offsets[c.S];
+        const unsigned long long *centre_offsets;
+        if ((rc = f.upload(f.R.ps_offsets, (const unsigned long long *)out_centre_offsets, (c.S + 1) * 8, centre_offsets)) ||
+            (rc = f.reserve(f.R.ps_packed, n_centres * 8, ps.packed_centres)))
+            return rc;
+        ps.centre_offsets = centre_offsets;
+        ps.packed_cover = ps.packed_centres + n_centres;
+        launch_patch_pack(ps, f.st);
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, download(out_centres, ps.packed_centres, n_centres * 4, f.st));
+        RS_HIP(ctx, download(out_cover, ps.packed_cover, n_centres * 4, f.st));
+        if (out_source) {
+            uint32_t n_rounds = 0;
+            launch_geodesic_restamp(gd, f.st);
+            if ((rc = gd_phase(f, gd, true, n_rounds))) return rc;
+        }
+        RS_HIP(ctx, download(out_dist, gd.dist, n_dots * 4, f.st));
+        RS_HIP(ctx, download(out_source, gd.source, n_dots * 4, f.st));
+    }
+    RS_HIP(ctx, download(out_free, gd.c.free, c.N * 4, f.st));
+    RS_HIP(ctx, download(out_sasa, gd.c.p.sasa, c.N * 4, f.st));
+    RS_HIP(ctx, hipStreamSynchronize(f.st));
+    ctx->ps_stats[0] = stats.picks;
+    ctx->ps_stats[1] = stats.steps;
+    ctx->ps_stats[2] = stats.overflows;
     return RSASA_OK;
 }
 
@@ -1177,6 +1282,39 @@ int rsasa_context_geodesic_rounds(rsasa_context_t *ctx, uint32_t *out_rounds)
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     out_rounds[0] = ctx->gd_rounds[0];
     out_rounds[1] = ctx->gd_rounds[1];
+    return RSASA_OK;
+}
+
+int rsasa_dot_patches(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                      const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, float link, float spacing,
+                      uint32_t max_centres, uint64_t *out_dot_offsets, uint64_t *out_centre_bound,
+                      uint64_t *out_centre_offsets, uint32_t *out_centres, float *out_cover, size_t centres_capacity,
+                      float *out_dist, uint32_t *out_source, size_t dots_capacity, uint32_t *out_free, float *out_sasa)
+{
+    return ps_run(ctx, x, y, z, radius, id, Form::one(n_atoms), probe_radius, n_points, link, spacing, max_centres,
+                    out_dot_offsets, out_centre_bound, out_centre_offsets, out_centres, out_cover, centres_capacity, out_dist,
+                    out_source, dots_capacity, out_free, out_sasa);
+}
+
+int rsasa_dot_patches_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                            const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                            size_t n_points, float link, float spacing, uint32_t max_centres, uint64_t *out_dot_offsets,
+                            uint64_t *out_centre_bound, uint64_t *out_centre_offsets, uint32_t *out_centres, float *out_cover,
+                            size_t centres_capacity, float *out_dist, uint32_t *out_source, size_t dots_capacity,
+                            uint32_t *out_free, float *out_atom_sasa)
+{
+    return ps_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, link, spacing,
+                    max_centres, out_dot_offsets, out_centre_bound, out_centre_offsets, out_centres, out_cover, centres_capacity,
+                    out_dist, out_source, dots_capacity, out_free, out_atom_sasa);
+}
+
+int rsasa_context_patch_stats(rsasa_context_t *ctx, uint64_t *out_stats)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (!out_stats) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "out_stats is NULL");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    for (int k = 0; k < 3; k++) out_stats[k] = ctx->ps_stats[k];
     return RSASA_OK;
 }
 

@@ -477,6 +477,69 @@ class Context:
         self._check(self._lib.rsasa_context_geodesic_rounds(self._h, ptr(rounds)))
         return int(rounds[0]), int(rounds[1])
 
+    # ---- dot patches (geodesic farthest-point sampling: where to put the centres of surface patches) ----
+    def _dot_patches(self, x, y, z, radius, ids, probe_radius, n_points, spacing, max_centres, link, sources,
+                     structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, _, _, radius, _), entry = self._entry("dot_patches", x, y, z, radius, ids, structure_offsets)
+        link = default_link(radius, probe_radius, n_points) if link is None else link
+        spacing = float(spacing)
+        if not spacing >= 0.0:
+            raise ValueError("spacing must be +inf or finite, and not negative")
+        max_centres = 0xFFFFFFFF if max_centres is None else int(max_centres)
+        if not 1 <= max_centres <= 0xFFFFFFFF:
+            raise ValueError("max_centres must be None (no bound) or in [1, 2^32 - 1]")
+        n = x.shape[0]
+        n_struct = 1 if structure_offsets is _SINGLE else len(structure_offsets) - 1
+        free, sasa = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+        dot_offsets, bound = np.zeros(n + 1, np.uint64), np.zeros(1, np.uint64)
+        centre_offsets = np.zeros(n_struct + 1, np.uint64)
+        # the first guess, as in dot_links; the second call is sized by what the first one wrote
+        dots_cap = min(n_points, 16) * n
+        cap = min(dots_cap, max_centres * n_struct)
+        for _ in range(2):
+            centres, cover = np.zeros(cap, np.uint32), np.zeros(cap, np.float32)
+            dist = np.zeros(dots_cap, np.float32)
+            source = np.zeros(dots_cap, np.uint32) if sources else None
+            rc = entry(probe_radius, n_points, link, spacing, max_centres, ptr(dot_offsets), ptr(bound), ptr(centre_offsets),
+                       ptr(centres), ptr(cover), cap, ptr(dist), ptr(source), dots_cap, ptr(free), ptr(sasa))
+            if rc != _capi.RSASA_ERR_BUFFER_TOO_SMALL:
+                break
+            dots_cap, cap = int(dot_offsets[-1]), int(bound[0])
+        self._check(rc)
+        d, k = int(dot_offsets[-1]), int(centre_offsets[-1])
+        return (dot_offsets, centre_offsets, centres[:k], cover[:k], dist[:d], source[:d] if sources else None, free, sasa)
+
+    def dot_patches(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, spacing: float = 6.0,
+                    max_centres=None, link=None, sources: bool = True):
+        """rsasa_dot_patches: (dot_offsets uint64[N + 1], centre_offsets uint64[2], centres uint32[K], cover float32[K],
+        dist float32[D], source uint32[D] or None, free uint32[N], sasa float32[N]).  Geodesic farthest-point sampling
+        of the accessible dots along dot_links' graph: the dot farthest from the centres so far (ties to the smallest
+        dot number; a dot at +inf first) becomes the next centre, cover[k] being its distance then, until every dot
+        lies within `spacing` of a centre (float32 compare; +inf: one centre per component) or the structure has
+        max_centres centres (None: no bound).  dist is dot_geodesics' result for the seed set `centres` with no limit,
+        source (sources=False: None) the smallest centre with a tight path - the patch of every dot.  centres and
+        source are dot numbers within the structure.  link None: default_link(radius, probe_radius, n_points).
+        patch_index() turns source into positions in `centres`, patch_table() sums the patches, dot_seeds_from()
+        gives the seed bytes with which dot_geodesics reproduces dist and source."""
+        return self._dot_patches(x, y, z, radius, ids, probe_radius, n_points, spacing, max_centres, link, sources)
+
+    def dot_patches_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100,
+                          spacing: float = 6.0, max_centres=None, link=None, sources: bool = True):
+        """rsasa_dot_patches_batch: dot_patches of every structure, each sampled on its own with max_centres centres at
+        most, all in one launch; centre_offsets uint64[S + 1] is batch-global, dist and source run over the dots of the
+        whole batch."""
+        return self._dot_patches(x, y, z, radius, ids, probe_radius, n_points, spacing, max_centres, link, sources,
+                                 structure_offsets)
+
+    def patch_stats(self):
+        """rsasa_context_patch_stats: (picks, relaxation steps summed over the structures, picks whose frontier outgrew
+        the sampler's queue) of this context's last dot_patches[_batch] call.  A measurement: the last two vary with
+        the GPU's schedule."""
+        stats = np.zeros(3, np.uint64)
+        self._check(self._lib.rsasa_context_patch_stats(self._h, ptr(stats)))
+        return int(stats[0]), int(stats[1]), int(stats[2])
+
     # ---- dot crowding (how much protein lies around each accessible dot, by distance bin) ----
     def _dot_crowding(self, x, y, z, radius, ids, probe_radius, n_points, edges, flags, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -1243,6 +1306,72 @@ def split_sasa(dot_offsets, labels, radius, probe_radius: float = 1.4, n_points:
     outer = np.bincount(owner[is_outer], weights=area[is_outer], minlength=n)
     cavity = np.bincount(owner[~is_outer], weights=area[~is_outer], minlength=n)
     return outer, cavity
+
+
+def _patch_args(dot_offsets, centre_offsets, centres, structure_offsets):
+    """The checked arguments of the patch helpers: (dot offsets int64[N + 1], first dot of every structure int64[S + 1],
+    centre offsets int64[S + 1], centres int64[K])."""
+    off = _dot_offsets(dot_offsets)
+    s_off = dot_structure_offsets(dot_offsets, structure_offsets)
+    c_off = np.ascontiguousarray(centre_offsets, dtype=np.uint64).astype(np.int64)
+    centres = np.ascontiguousarray(centres, dtype=np.uint32).astype(np.int64)
+    if c_off.ndim != 1 or c_off.shape != s_off.shape or c_off[0] != 0 or (np.diff(c_off) < 0).any():
+        raise ValueError(f"centre_offsets must be a 1-D array of {s_off.shape[0]} entries, non-decreasing from 0")
+    if centres.ndim != 1 or centres.shape[0] != int(c_off[-1]):
+        raise ValueError(f"centres must be a 1-D array of centre_offsets[-1] = {int(c_off[-1])} entries")
+    if (centres >= np.repeat(np.diff(s_off), np.diff(c_off))).any():
+        raise ValueError("a centre is no dot number of its structure")
+    return off, s_off, c_off, centres
+
+
+def dot_seeds_from(centre_offsets, centres, dot_offsets, structure_offsets=None) -> np.ndarray:
+    """uint8[D]: the seed bytes that mark the centres of dot_patches[_batch] - given to dot_geodesics[_batch] with no
+    limit they reproduce its dist and source.  structure_offsets None: one structure."""
+    off, s_off, c_off, centres = _patch_args(dot_offsets, centre_offsets, centres, structure_offsets)
+    seeds = np.zeros(int(off[-1]), np.uint8)
+    seeds[centres + np.repeat(s_off[:-1], np.diff(c_off))] = 1
+    return seeds
+
+
+def patch_index(dot_offsets, source, centre_offsets, centres, structure_offsets=None) -> np.ndarray:
+    """int64[D]: for every dot the batch-global position in `centres` of its centre source[d] (dot_patches[_batch] with
+    sources=True), -1 where source is 0xFFFFFFFF (a dot no centre reaches: max_centres cut the sampling short).
+    np.bincount(patch_index, weights=values) sums per-dot values by patch.  structure_offsets None: one structure."""
+    off, s_off, c_off, centres = _patch_args(dot_offsets, centre_offsets, centres, structure_offsets)
+    source = np.ascontiguousarray(source, dtype=np.uint32).astype(np.int64)
+    if source.ndim != 1 or source.shape[0] != int(off[-1]):
+        raise ValueError(f"source must be a 1-D array of dot_offsets[-1] = {int(off[-1])} entries")
+    base = np.repeat(s_off[:-1], np.diff(s_off))
+    where = np.full(int(off[-1]) + 1, -1, np.int64)          # batch-wide dot -> position in centres; the last: no dot
+    where[centres + np.repeat(s_off[:-1], np.diff(c_off))] = np.arange(centres.shape[0])
+    none = source == 0xFFFFFFFF
+    if (source[~none] >= (np.repeat(np.diff(s_off), np.diff(s_off)))[~none]).any():
+        raise ValueError("a source is no dot number of its structure")
+    out = where[np.where(none, int(off[-1]), source + base)]
+    if (out[~none] < 0).any():
+        raise ValueError("a source is no centre of its structure")
+    return out
+
+
+def patch_table(dot_offsets, source, centre_offsets, centres, radius, probe_radius: float = 1.4, n_points: int = 100,
+                structure_offsets=None):
+    """The patches of dot_patches[_batch], one row per centre in the order of `centres`: (structure int64[K],
+    centre uint32[K], dots int64[K], atoms int64[K], area float64[K]) - the structure of the centre, its dot number,
+    how many dots have it as their source, how many atoms own one of those, and the float64 sum of 4 pi R^2 / n_points
+    over them in dot order (R = radius + probe_radius in float32, of the dot's atom; component_table's area).  The rows
+    of a structure sum to the area of its reached dots.  structure_offsets None: one structure."""
+    which = patch_index(dot_offsets, source, centre_offsets, centres, structure_offsets)
+    off, _, so, owner, area = _dots(dot_offsets, np.zeros(which.shape[0], np.uint32), radius, probe_radius, n_points,
+                                    structure_offsets)
+    c_off = np.ascontiguousarray(centre_offsets, dtype=np.uint64).astype(np.int64)
+    k = int(c_off[-1])
+    hit = which >= 0
+    dots = np.bincount(which[hit], minlength=k).astype(np.int64)
+    a = np.bincount(which[hit], weights=area[hit], minlength=k).astype(np.float64)
+    pairs = np.unique((which[hit] << 32) | owner[hit])
+    atoms = np.bincount(pairs >> 32, minlength=k).astype(np.int64)
+    structure = np.repeat(np.arange(so.shape[0] - 1, dtype=np.int64), np.diff(c_off))
+    return structure, np.ascontiguousarray(centres, dtype=np.uint32), dots, atoms, a
 
 
 def sas_volume(vectors, free, x, y, z, radius, probe_radius: float = 1.4, n_points: int = 100, structure_offsets=None,
