@@ -28,7 +28,11 @@
 // and such an atom's dots link nothing.  Without the margins, or with a longer link, every atom of the reach is staged.
 // (k_component_link has no such cut and stays as it is.)
 // k_dot_link writes the loops of sh_sweep (shell_sweep.h: the driver and its contract) out as k_component_link does, and
-// must follow a change there by hand; it was copied with them and not measured under the driver.
+// follows a change there and in k_component_link: the two bodies are the same text but for the staged atoms, the lane's
+// state, what an accepted pair does and what the lane stores.  One function template for both, the four differences as
+// inline members of a policy struct, was built and timed on the MI355X (profiles/dot_pairs_ab.txt): the same registers
+// and LDS, k_component_link 5 % and the count 11 % faster, but of the fill and the weights one was always slower than
+// here (2 to 3 %, or 0.4 % against a run-to-run range of 0.1 %), whichever place the policy's per-wave set-up took.
 //
 // Ordered pairs or atomics.  k_component_link takes every unordered pair of atoms once; lists need both directions.  With
 // unordered pairs the dot of the staged atom would get its entry from a lane that does not own it: a global atomic per

@@ -17,8 +17,10 @@
 //   k_component_link (components.hip)  a fixed reach, shells 0 .. s_end, computed before the sweep; 9 % slower.  It does
 //                                      not take sh_frame either: with the frame alone its listing changes (936
 //                                      instructions for 932), and that build was not timed.
-//   k_dot_link (geodesics.hip)         k_component_link's loops and reach, copied with them: the three instantiations were
-//                                      never run through the driver, so the 9 % are the components kernel's, not theirs.
+//   k_dot_link (geodesics.hip)         k_component_link's loops and reach.  The three instantiations were not run through
+//                                      the driver (the 9 % are the components kernel's); sharing one written-out body
+//                                      with k_component_link was timed, and the fill or the weights came out slower
+//                                      (profiles/dot_pairs_ab.txt), so the body stands twice.
 // One wave per cell-sorted atom i.  The cells of its structure's grid are swept in Chebyshev shells s = 0, 1, 2, ... around
 // its own cell: shell s is the cells at distance exactly s, cut into x-runs of cell starts as nb_runs cuts the 5x5x5 block
 // - a row (y, z) on the rim of the shell's square gives the whole run [cx - s, cx + s], a row inside it the two cells

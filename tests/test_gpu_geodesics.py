@@ -110,6 +110,36 @@ def test_own_dots_in_several_chunks(ctx, n_points):
     _check_links(_links(ctx, c, n_points), _lists("multi_chunk", n_points), c, n_points)
 
 
+@pytest.mark.parametrize("n_points", [100, cc.CHUNK_POINTS[0]])
+@pytest.mark.parametrize("name", ["tiny", "overlap_batch"])
+def test_the_lists_span_the_components_of_the_same_sweep(ctx, name, n_points):
+    """k_dot_link and k_component_link hold the same sweep twice (reach, staging, chunk loops, edge test), and a change
+    made in one of them only shows here: a union-find on the host over the lists, the smallest dot of a tree its root,
+    gives the labels of surface_components_batch at the same link, element for element.  65 points: an atom's own dots
+    take two chunks of 64 lanes, the second a single point."""
+    import rustsasa_amd
+    c = _case(name)
+    link = _link(c, n_points)
+    off, loff, ent, _, _ = _links(ctx, c, n_points, link)
+    c_off, labels, _, _ = ctx.surface_components_batch(*c.cols, c.so, c.probe, n_points, link)
+    assert np.array_equal(off, c_off) and len(labels) == int(off[-1]) > 0
+    first = rustsasa_amd.dot_structure_offsets(off, c.so)
+    a, b = rustsasa_amd.edge_index(loff, ent, first)
+    parent = list(range(len(labels)))
+
+    def find(d):
+        while parent[d] != d:
+            parent[d] = d = parent[parent[d]]
+        return d
+
+    for u, v in zip(a.tolist(), b.tolist()):
+        u, v = find(u), find(v)
+        parent[max(u, v)] = min(u, v)
+    roots = np.array([find(d) for d in range(len(labels))], np.int64)
+    base = np.repeat(first[:-1], np.diff(first))
+    assert len(a) > 0 and np.array_equal(roots - base, labels.astype(np.int64))
+
+
 def test_zero_weight_edges_at_link_zero(ctx):
     c = _case("twins")
     got = _links(ctx, c, 100, 0.0)
