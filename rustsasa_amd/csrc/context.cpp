@@ -138,7 +138,7 @@ namespace rsasa {
 int fail(rsasa_context *ctx, int code, const char *what, hipError_t e)
 {
     if (ctx) {
-        // several threads may share a context (host_api.cpp runs two workers on one): the message
+        // several threads may share a context (host/files_mode.cpp runs two workers on one): the message
         // is written and read under the context's (recursive) mutex
         std::lock_guard<std::recursive_mutex> lk(ctx->mu);
         ctx->last_error = what;

@@ -194,6 +194,21 @@ int main(int argc, char **argv)
         std::printf("%s\n", sasa_result_to_json(v).c_str());
         return 0;
     }
+    if (argc >= 4 && std::string(argv[1]) == "after-throw") {
+        // test hook, no GPU: directory mode reads <file the reader throws on> on this thread (one parse thread is the
+        // caller's; the file's error stays in the discarded result), then the same thread reads <good file>: its
+        // occupancies are printed and must be the file's - nothing of the failed read may linger
+        (void)SASAOptions<ResidueLevel>().process_files({argv[2]}, 1);
+        const Structure s = Structure::open(argv[3]);
+        std::printf("[");
+        bool first = true;
+        for (const auto &c : s.chains)
+            for (const auto &r : c.residues)
+                for (const auto &f : r.conformers)
+                    for (const auto &a : f.atoms) { std::printf("%s%.9g", first ? "" : ",", a.occupancy); first = false; }
+        std::printf("]\n");
+        return 0;
+    }
     if (argc >= 4 && std::string(argv[1]) == "files") {
         const std::string level = argv[2];
         try {

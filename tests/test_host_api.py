@@ -309,7 +309,7 @@ def test_process_files_companion_context_runs_with_the_callers_settings(tmp_path
 @pytest.mark.gpu
 def test_process_files_with_radii_from_occupancy_reads_the_occupancies(tmp_path):
     """Directory mode skips the conversion of occupancy / b-factor columns unless an option needs them
-    (host_api.cpp t_skip_occupancy_and_bfactor): with radii from the occupancy column the values must be the
+    (prepare_text's skip_occupancy_and_bfactor argument): with radii from the occupancy column the values must be the
     single-file results of the same option."""
     paths = [sio.data_path(n) for n in ("1jcd.pdb", "151L_H3.pdb", "example.cif")]
     lst = str(tmp_path / "files.txt")
@@ -331,7 +331,7 @@ def _prepare_json(path, level, fast, *opts):
 
 
 def test_directory_modes_short_cut_equals_the_general_reader(tmp_path):
-    """process_files reads plain PDB files straight into the kept atoms (host_api.cpp fast_pdb_prepare) and leaves
+    """process_files reads plain PDB files straight into the kept atoms (prepare.cpp fast_pdb_prepare) and leaves
     everything else to the general reader + selection.  Both must hand the GPU the same atoms (bit patterns of x, y, z,
     radius; ids), the same segment ends and the same result metadata - on the fixtures, under the options the
     reference tests, and on mutants that hit each of the short cut's exits (alternate locations, chains and residues
@@ -404,7 +404,7 @@ def _pdb_to_mmcif(pdb_path, quote_names=True):
 
 
 def test_directory_modes_mmcif_short_cut_equals_the_general_reader(tmp_path):
-    """The same for mmCIF text (host_api.cpp fast_cif_prepare): the reference's AlphaFold fixture, the PDB fixtures
+    """The same for mmCIF text (prepare.cpp fast_cif_prepare): the reference's AlphaFold fixture, the PDB fixtures
     rewritten as `_atom_site` loops, and mutants of them that hit the short cut's exits - an alternate location, a chain
     that comes back, rows swapped, a row with a token too few or too many, no element symbol, an atom without a radius,
     a second model, a residue number that goes back, a second name inside a residue, an insertion code, a serial number
@@ -473,6 +473,107 @@ def test_directory_modes_mmcif_short_cut_equals_the_general_reader(tmp_path):
             path.write_text("\n".join(mut))
             compare(path, f"{name} mutant {kind}", (1, 2), option_sets[:2] if kind % 2 else option_sets[2:])
     assert n_fast > 60 and n_cases - n_fast > 60, (n_fast, n_cases)  # both routes were exercised
+
+
+def _element_forms_pdb(nameless):
+    """Thirteen hand-written records whose element columns take every form the element rule distinguishes.  Atoms of
+    ALA / GLY carry ProtOr names (a radius whatever the symbol says), the HETATM records do not (van-der-Waals radius of
+    the WHOLE upper-cased symbol).  `nameless`: one more record without a symbol whose name has no letter - no element."""
+    rows = [  # record, name, residue, number, element columns 77-78
+        ("ATOM", "N", "ALA", 1, " N"),
+        ("ATOM", "CA", "ALA", 1, " H"),      # hydrogen
+        ("ATOM", "C", "ALA", 1, " h"),       # hydrogen, lower case
+        ("ATOM", "O", "ALA", 1, "HG"),       # two letters that start with H: mercury, helium, holmium - not hydrogen
+        ("ATOM", "CB", "ALA", 1, "HE"),
+        ("ATOM", "N", "GLY", 2, "HO"),
+        ("ATOM", "CA", "GLY", 2, "Zn"),      # mixed case
+        ("ATOM", "C", "GLY", 2, " C"),       # (the mmCIF text gives this one the three-character symbol ZN2)
+        ("ATOM", "O", "GLY", 2, "  "),       # no symbol: the name's first letter, O
+        ("ATOM", "1H", "GLY", 2, "  "),      # no symbol: the name's first LETTER, H - hydrogen
+        ("HETATM", "ZN", "ZN", 3, "Zn"),     # no ProtOr name: the look-up takes ZN
+        ("HETATM", "HG", "HG", 4, "HG"),     # ... and HG, 2.45 - H alone would be 1.20
+        ("HETATM", "X1", "UNK", 5, " h"),    # a hetero hydrogen
+    ]
+    if nameless:
+        rows.insert(9, ("ATOM", "123", "GLY", 2, "  "))
+    return "".join("%-6s%5d %-4s %3s A%4d    %8.3f%8.3f%8.3f  0.75 10.00          %2s  \n" %
+                   (rec, k + 1, name if len(name) == 4 else " " + name, res, seq, 1.5 * k, 0.25 * k, -0.5 * k, el)
+                   for k, (rec, name, res, seq, el) in enumerate(rows)) + "END\n"
+
+
+@pytest.mark.parametrize("fmt", ["pdb", "cif"])
+def test_element_forms_decide_the_same_on_both_routes(tmp_path, fmt):
+    """One element rule behind both short cuts (prepare.cpp LightModel::keep_atom) and the general reader's
+    set_element + selection: the symbol's first character in upper case, hydrogen only when the symbol is that one
+    character, without a symbol the first letter of the name, and the van-der-Waals look-up with the whole upper-cased
+    symbol.  Short cut and general reader must agree on atoms, segment ends, model and error; the short cut must
+    TAKE the file where every atom has an element and leave the one with a letterless name to the general reader,
+    which reports the missing element.  The kept-atom counts are written out by hand."""
+    option_sets = {(): 7,                                                # ATOM records that are not hydrogen (H, h, 1H)
+                   ("--allow-vdw-fallback",): 7,
+                   ("--include-hydrogens", "--allow-vdw-fallback"): 10,  # every ATOM record
+                   ("--include-hetatms", "--allow-vdw-fallback"): 9}     # + ZN and HG; the hetero h stays out
+    for nameless in (False, True):
+        path = tmp_path / f"forms_{int(nameless)}.pdb"
+        path.write_text(_element_forms_pdb(nameless))
+        if fmt == "cif":
+            lines = _pdb_to_mmcif(path).split("\n")
+            i = next(k for k, l in enumerate(lines) if l.startswith("ATOM 8 C C "))
+            lines[i] = lines[i].replace("ATOM 8 C C ", "ATOM 8 ZN2 C ", 1)
+            path = tmp_path / f"forms_{int(nameless)}.cif"
+            path.write_text("\n".join(lines))
+        for opts, n_kept in option_sets.items():
+            for level in (1, 2):
+                a, b = _prepare_json(path, level, True, *opts), _prepare_json(path, level, False, *opts)
+                took = a.pop("fast")
+                assert b.pop("fast") is False
+                assert a == b, (nameless, opts, level, len(a["atoms"]), len(b["atoms"]), a["error"], b["error"])
+                if nameless:
+                    assert took is False and a["error"] == 1, (opts, level, took, a["error"])  # ElementMissing
+                else:
+                    assert took is True and a["error"] == 0, (opts, level, took, a["error"])
+                    assert len(a["atoms"]) == n_kept, (opts, level, len(a["atoms"]))
+                    assert a["seg_end"][-1] == n_kept and len(a["seg_end"]) == (1 if level == 2 else 5)
+                    if "--include-hetatms" in opts:  # the look-up took the whole symbol: ZN and HG, not Z (none) or H (1.20)
+                        radii = [float.fromhex(r[3]) for r in a["atoms"][-2:]]
+                        assert radii == [float(np.float32(2.39)), float(np.float32(2.45))], radii
+
+
+def _cif_without_x(tmp_path):
+    """An mmCIF file whose `_atom_site` loop has no Cartn_x column: the general reader throws on it."""
+    bad = tmp_path / "no_x.cif"
+    bad.write_text(_pdb_to_mmcif(sio.data_path("1jcd.pdb")).replace("_atom_site.Cartn_x\n", "_atom_site.Cartn_q\n"))
+    return str(bad)
+
+
+def test_a_reader_that_throws_leaves_nothing_behind_on_its_thread(tmp_path):
+    """Directory mode asks the readers to skip occupancies and b-factors; that request is an argument of the call
+    (host_internal.h read_pdb_text / read_mmcif_text), so a reader that throws cannot leave it switched on for the
+    thread's later callers.  `sasa_host_cli after-throw` reads the throwing file in directory mode on its own thread,
+    then opens a good file on the same thread: the occupancies must be the file's, not the default 1.0.  No GPU."""
+    good = tmp_path / "occ.pdb"
+    occs = [0.25, 0.5, 0.75, 0.3]
+    good.write_text("".join("ATOM  %5d  CA  ALA A%4d    %8.3f%8.3f%8.3f%6.2f%6.2f           C  \n" % (k + 1, k + 1, 3.8 * k, 0.0, 0.0, o, 20.0)
+                            for k, o in enumerate(occs)) + "END\n")
+    p = subprocess.run([CLI, "after-throw", _cif_without_x(tmp_path), str(good)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[:500]
+    assert json.loads(p.stdout) == occs
+
+
+@pytest.mark.gpu
+def test_process_files_goes_on_unharmed_after_a_reader_that_throws(tmp_path):
+    """The same in directory mode itself: one parse thread reads a file the general reader throws on, then two good
+    ones - they must get their single-file values, the first its own error."""
+    paths = [_cif_without_x(tmp_path), sio.data_path("1jcd.pdb"), sio.data_path("example.cif")]
+    lst = str(tmp_path / "files.txt")
+    open(lst, "w").write("\n".join(paths) + "\n")
+    p = subprocess.run([CLI, "files", "residue", lst, "--threads", "1", "--full"], capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[:500]
+    got = json.loads(p.stdout)
+    assert got["n_ok"] == 2 and got["results"][0] == {"error": 7}
+    for path, r in zip(paths[1:], got["results"][1:]):
+        single = run_cli("residue", os.path.basename(path))["Residue"]
+        assert np.array_equal(np.array(r, np.float32), np.array([x["value"] for x in single], np.float32)), path
 
 
 def test_fixed_column_decimals_equal_the_general_parser(tmp_path):

@@ -51,9 +51,9 @@ def freesasa_chains(path):
 
 
 def vdw_table():
-    """The host API's van-der-Waals table (host_api.cpp vdw_radius), read from its source."""
+    """The host API's van-der-Waals table (radii.cpp vdw_radius), read from its source."""
     import re
-    src = open(os.path.join(ROOT, "rustsasa_amd", "csrc", "host", "host_api.cpp")).read()
+    src = open(os.path.join(ROOT, "rustsasa_amd", "csrc", "host", "radii.cpp")).read()
     body = src[src.index("bool vdw_radius("):]
     body = body[:body.index("return false;")]
     return {m.group(1): float(m.group(2)) for m in re.finditer(r'\{"([A-Z]+)",\s*([0-9.]+)f\}', body)}

@@ -333,7 +333,8 @@ def main():
         lib = os.path.join(ROOT, "rustsasa_amd", "lib")
         src = os.path.join(ROOT, "rustsasa_amd", "csrc", "host")
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                               "-I", os.path.join(ROOT, "include"), os.path.join(src, "host_api.cpp"),
+                               "-I", os.path.join(ROOT, "include"),
+                               *(os.path.join(src, f) for f in ("radii.cpp", "reader.cpp", "prepare.cpp", "writer.cpp", "files_mode.cpp")),
                                os.path.join(src, "sasa_host_cli.cpp"), "-o", cli, "-L", lib, "-lrustsasa_amd",
                                "-Wl,-rpath," + lib, "-lpthread"])
         for name in ("1jcd.pdb", "example.cif"):  # the model's copy / move rules under the sanitizers
