@@ -145,6 +145,41 @@ int rsasa_context_bind_thread(rsasa_context_t *ctx, int *out_numa_node);
  * context per GPU) and want them to give the same values. */
 int rsasa_context_clone_settings(rsasa_context_t *dst, rsasa_context_t *src);
 
+/* Argument rules (every entry point of the hot path, rsasa_batch_enqueue and
+ * rsasa_segment_sums).  A call is answered by the FIRST rule it breaks, in the
+ * order listed for its entry point, with RSASA_ERR_INVALID_ARGUMENT and the
+ * rule's message as the context's last error - before the context is locked,
+ * a buffer reserved, a byte uploaded, an output written, or a column or
+ * offset read for anything but a rule.  The rules:
+ *   - n_points in [1, 2^24]; probe_radius finite and >= 0 (-0.0 is 0);
+ *     n_points comes before probe_radius;
+ *   - sizes (atoms, structures, residues, frames, values, segments) below
+ *     0xFFFFFFF0;
+ *   - structure offsets: not NULL, spanning [0, n_atoms] - the first entry is
+ *     0 on EVERY path, and for a device batch the last is n_atoms -, then
+ *     non-decreasing: the span comes before the order;
+ *   - residue offsets: the last not past the atoms, then non-decreasing.
+ * Order of the verdicts:
+ *   rsasa_calculate_sasa_internal, _soa: n_atoms >= 0xFFFFFFF0 and a missing
+ *     out_sasa (for _internal: or atoms) are refused without a message; columns
+ *     NULL; n_atoms == 0 is RSASA_OK (whatever n_points is); n_points; probe.
+ *   rsasa_calculate_sasa_batch (and, from rsasa_host_batch_wait, a batch of
+ *     rsasa_host_batch_enqueue, which itself checks nothing): structure_offsets
+ *     NULL; columns NULL; out_residue_sasa NULL; no output requested; no atoms
+ *     and no residues is RSASA_OK; residue offsets; n_points; probe; sizes; the
+ *     structure offsets' span; their order.
+ *   rsasa_calculate_sasa_trajectory: no frames or no atoms is RSASA_OK; xyz /
+ *     radius NULL; out_residue_sasa NULL; no output requested; sizes; residue
+ *     offsets; n_points; probe.
+ *   rsasa_batch_enqueue: batch NULL; n_points; probe; sizes; columns NULL;
+ *     structure_offsets_host NULL; span; order; atoms without structures;
+ *     out_residue_sasa NULL.
+ *   rsasa_segment_sums: no segments is RSASA_OK; NULL argument; sizes and the
+ *     last offset; the offsets' order.
+ * The rules answer before device batches in flight on the context are waited
+ * for: an invalid call does not report an earlier batch's deferred error - that
+ * error stays with its batch for the next rsasa_batch_wait. */
+
 /* ---- the hot path, one structure per call ------------------------------ */
 
 /* Non-finite input (every entry point of the hot path, every kernel).

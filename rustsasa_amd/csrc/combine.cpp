@@ -176,11 +176,11 @@ int run_block(Combiner::Lane &lane, Block &b, int device, std::string *error)
 
 }  // namespace
 
+// Assumes the per-structure calls' rule (check_structure_call, sasa_checks.h): atoms, their columns or records, n_points
+// and probe in range.
 int combine_call(rsasa_context *ctx, const SmallSource &in, size_t n_atoms, float probe, size_t n_points, float *out)
 {
-    if (ctx->device < 0 || ctx->device >= 64 || n_atoms == 0 || n_atoms > kCombineCallAtoms || n_points == 0 || n_points > (1u << 24) ||
-        !(probe >= 0.0f) || !std::isfinite(probe))
-        return kNotCombined;
+    if (ctx->device < 0 || ctx->device >= 64 || n_atoms > kCombineCallAtoms) return kNotCombined;
     const uint64_t t_in = now_ns();
     Request rq;
     rq.in = in;

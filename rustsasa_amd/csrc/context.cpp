@@ -2,6 +2,7 @@
 // sphere lattice cache, batch enqueue / wait.  Host code only; the kernels
 // live in kernels.hip.  There is no CPU compute path in this library.
 #include "engine_internal.h"
+#include "sasa_checks.h"
 
 namespace rsasa {
 
@@ -888,44 +889,21 @@ int rsasa_context_ids_dropped(rsasa_context_t *ctx, uint64_t *out_batches)
 int rsasa_batch_enqueue(rsasa_context_t *ctx, const rsasa_device_batch_t *batch,
                         float probe_radius, size_t n_points, void *hip_stream)
 {
-    return rsasa::batch_enqueue(ctx, batch, probe_radius, n_points, hip_stream, false);
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    if (const char *msg = check_device_batch(batch, probe_radius, n_points)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, msg);
+    return enqueue_checked(ctx, *batch, probe_radius, n_points, hip_stream);
 }
 
 }  // extern "C"
 
-// rsasa_batch_enqueue; ids_needed_known: the caller has looked at the ids itself and found that they matter (the host
-// paths check while the coordinates cross the link): the device does not check again
-int rsasa::batch_enqueue(rsasa_context *ctx, const rsasa_device_batch_t *batch, float probe_radius, size_t n_points, void *hip_stream,
-                         bool ids_needed_known)
+// rsasa_batch_enqueue behind its rule.  `batch` has passed check_device_batch with this probe and n_points, or was built
+// from arguments that passed their entry point's rule (a host batch of one sub-batch, a trajectory's chunk of frames):
+// nothing here looks again.
+int rsasa::enqueue_checked(rsasa_context *ctx, const rsasa_device_batch_t &batch, float probe_radius, size_t n_points, void *hip_stream)
 {
-    int rc = resolve_ctx(ctx);
-    if (rc) return rc;
+    int rc;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
-    if (!batch) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "batch is NULL");
-    if (n_points == 0 || n_points > (1u << 24))
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^24]");
-    if (!(probe_radius >= 0.0f) || !std::isfinite(probe_radius))
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "probe_radius must be finite and >= 0");
-    if (batch->n_atoms >= 0xFFFFFFF0ull || batch->n_structures >= 0xFFFFFFF0ull ||
-        batch->n_residues >= 0xFFFFFFF0ull)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "batch too large for 32-bit indices");
-    if (batch->n_atoms && (!batch->x || !batch->y || !batch->z || !batch->radius))
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "coordinate / radius arrays are NULL");
-    if (batch->n_structures && !batch->structure_offsets_host)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets_host is NULL");
-    if (batch->n_structures) {
-        const uint32_t *o = batch->structure_offsets_host;
-        if (o[0] != 0 || o[batch->n_structures] != batch->n_atoms)
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must span [0, n_atoms]");
-        for (size_t s = 0; s < batch->n_structures; s++)
-            if (o[s] > o[s + 1])
-                return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
-    } else if (batch->n_atoms) {
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "atoms without structures");
-    }
-    if (batch->n_residues && batch->residue_offsets && !batch->out_residue_sasa)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "out_residue_sasa is NULL");
-
     RS_DEVICE(ctx);
     // Up to two batches in flight, each in its own workspace; a third waits for the oldest one.
     while (ctx->n_pending >= rsasa_context::kInFlight)
@@ -935,13 +913,12 @@ int rsasa::batch_enqueue(rsasa_context *ctx, const rsasa_device_batch_t *batch, 
         RS_HIP(ctx, new_stream(ctx, &ctx->stream2.h, 2));
     Pending &pd = ctx->pending[ctx->head ^ (ctx->n_pending ? 1 : 0)];
     pd = Pending{};
-    pd.batch = *batch;
+    pd.batch = batch;
     pd.probe = probe_radius;
     pd.n_points = n_points;
     pd.stream = hip_stream ? (hipStream_t)hip_stream : (w ? ctx->stream2 : ctx->stream);
     pd.ws = w;
     pd.solo_ok = true;  // (rsasa_batch_wait runs a batch again when the id-less launch was the wrong guess: wait_one)
-    pd.ids_needed_known = ids_needed_known;
     rc = enqueue_batch(ctx, pd, ctx->slot[w]);
     pd.active = (rc == RSASA_OK);
     if (pd.active) ctx->n_pending++;
@@ -991,14 +968,9 @@ int rsasa_segment_sums(rsasa_context_t *ctx, const float *values, size_t n_value
 {
     int rc = resolve_ctx(ctx);
     if (rc) return rc;
-    if (n_segments == 0) return RSASA_OK;
-    if (!offsets || !out || (n_values && !values))
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (n_values >= 0xFFFFFFF0ull || n_segments >= 0xFFFFFFF0ull || offsets[n_segments] > n_values)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "offsets exceed n_values");
-    for (size_t k = 0; k < n_segments; k++)
-        if (offsets[k] > offsets[k + 1])
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "offsets must be non-decreasing");
+    bool empty;
+    if (const char *msg = check_segments(values, n_values, offsets, n_segments, out, empty)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, msg);
+    if (empty) return RSASA_OK;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     RS_DEVICE(ctx);
     if (ctx->n_pending && (rc = wait_pending(ctx))) return rc;

@@ -612,8 +612,8 @@ int wait_oldest(rsasa_context *ctx);
 int wait_pending(rsasa_context *ctx);
 int resolve_ctx(rsasa_context *&ctx);
 int context_create(int device, int own_queues, rsasa_context_t **out_ctx);  // own_queues: rsasa_context::own_queues
-int batch_enqueue(rsasa_context *ctx, const rsasa_device_batch_t *batch, float probe_radius, size_t n_points, void *hip_stream,
-                  bool ids_needed_known);  // rsasa_batch_enqueue with the host's verdict on the ids
+// rsasa_batch_enqueue behind its rule: for a descriptor that passed check_device_batch (sasa_checks.h) or was built from checked arguments
+int enqueue_checked(rsasa_context *ctx, const rsasa_device_batch_t &batch, float probe_radius, size_t n_points, void *hip_stream);
 
 // ---- the small-batch path (host_batch.cpp), shared with the call combiner (combine.cpp) ----
 // Where a small batch's atoms come from: columns (the SoA entry points) or rsasa_atom_t records (rsasa_calculate_sasa_internal:

@@ -1,6 +1,7 @@
 // Host-pointer entry points of the C ABI (include/rustsasa_amd.h): the small-batch path, the pipelined host batch
 // (rsasa_calculate_sasa_batch), the stream of host batches, the per-structure calls and trajectories.  Host code only.
 #include "engine_internal.h"
+#include "sasa_checks.h"
 
 namespace {
 
@@ -228,14 +229,14 @@ int small_run(rsasa_context *ctx, const SmallLayout &l, const Lattice &lat, cons
 // dozen small copies.  Here the host computes the bounding boxes and grids itself (N is small),
 // so the device needs ONE upload (inputs + grids + status, through pinned staging), four
 // launches (LDS binning, the two occlusion kernels, residue sums) and one download.
-// kNotSmall: the batch is the general path's (too large, or anything unusual, which that path validates and reports).
+// kNotSmall: the batch is the general path's (too large, timed, or a grid the LDS windows do not take).
+// Assumes the entry point's rule (sasa_checks.h): the offsets start at 0 and do not fall, the columns hold so[S] atoms,
+// n_points and probe are in range.
 int run_small_host_batch(rsasa_context *ctx, const SmallSource &in, const uint32_t *so, size_t S,
                          float probe, size_t n_points, float *out_atom, const uint32_t *ro, size_t R,
                          float *out_res)
 {
-    if (S == 0 || S > kSmallStructures || so[0] != 0 || n_points == 0 || n_points > (1u << 24) ||
-        !(probe >= 0.0f) || !std::isfinite(probe) || ctx->timing)
-        return kNotSmall;
+    if (S == 0 || S > kSmallStructures || ctx->timing) return kNotSmall;
     const size_t N = so[S];
     if (N == 0 || N > kSmallAtoms) return kNotSmall;
     // (the single-structure call - most calls - keeps its one grid on the stack)
@@ -248,7 +249,6 @@ int run_small_host_batch(rsasa_context *ctx, const SmallSource &in, const uint32
     size_t W = 0;
     unsigned long long total_cells = 0;  // 16-bit entries of the cell array
     for (size_t s = 0; s < S; s++) {
-        if (so[s] > so[s + 1]) return kNotSmall;  // (the general path reports it)
         if (!small_structure_grid(in, so[s], so[s + 1], probe, &grids[s])) return kNotSmall;
         grids[s].atom_begin = so[s];
         grids[s].sorted_base = so[s];
@@ -283,11 +283,6 @@ int run_small_host_batch(rsasa_context *ctx, const SmallSource &in, const uint32
 }
 
 }  // namespace rsasa
-
-extern "C" {
-
-
-}  // extern "C"
 
 namespace {
 
@@ -387,7 +382,8 @@ bool is_pinned(const void *p)
 //   stage()    device buffers, pinned blocks, what the host prepares per sub-batch (id folds, radius codes) and how results leave
 //   run_one()  a batch that is one sub-batch: upload, kernels, wait, copy out
 //   run_piped() several sub-batches on three streams: copy-in (c + 1), compute (c), copy-out (c - 1)
-// The context is locked and its device current for the object's lifetime.
+// The context is locked and its device current for the object's lifetime.  The arguments have passed check_host_batch
+// (sasa_checks.h) and are not empty: no step looks at them as outside input again.
 struct HostBatch {
     static constexpr int kSlots = rsasa_context::kSlots;
     static constexpr size_t kTableWords = 256;  // a sub-batch's offsets block on the device: radius table | residue offsets
@@ -545,7 +541,7 @@ struct HostBatch {
         if (piped && id && !tuning_env("RSASA_NO_ID_FOLD")) {
             Lattice lat_probe;
             void *dp = nullptr;
-            if (n_points >= 1 && n_points <= (1u << 24) && get_lattice(ctx, n_points, &lat_probe) == RSASA_OK &&
+            if (get_lattice(ctx, n_points, &lat_probe) == RSASA_OK &&
                 hipHostGetDevicePointer(&dp, const_cast<uint64_t *>(id), 0) == hipSuccess && dp) {
                 fold_ids = true;
                 for (size_t c = 0; c + 1 < cut.size(); c++) fold_ids &= occlusion_uses_mx(ctx->tuning, lat_probe, (uint32_t)atoms_of(c));
@@ -585,7 +581,7 @@ struct HostBatch {
         // coding workers look while they fold; one large sub-batch is checked by the same workers while its coordinates
         // cross the link (then its 8 bytes of id per atom stay on the host); anything smaller is checked on the device.
         check_ids = id && !tuning_env("RSASA_NO_ID_CHECK");
-        if (!piped && check_ids && cut.size() == 2 && structure_offsets[n_structures] >= 262144u && n_points >= 1 && n_points <= (1u << 24)) {
+        if (!piped && check_ids && cut.size() == 2 && structure_offsets[n_structures] >= 262144u) {
             Lattice lat_probe;
             host_check = get_lattice(ctx, n_points, &lat_probe) == RSASA_OK &&
                          occlusion_uses_mx(ctx->tuning, lat_probe, structure_offsets[n_structures]);
@@ -746,7 +742,7 @@ struct HostBatch {
             bt.out_neighbor_counts = nullptr;
             // (ids that do not rise are not yet ids that matter: the device's own check - its hash tables for ids in no order -
             // still runs on them; the host's pass only ever proves the droppable case)
-            if ((rc = batch_enqueue(ctx, &bt, probe_radius, n_points, nullptr, false))) return rc;
+            if ((rc = enqueue_checked(ctx, bt, probe_radius, n_points, nullptr))) return rc;
             if ((rc = rsasa_batch_wait(ctx))) return rc;
         }
         if ((rc = copy_out(0))) return rc;
@@ -879,14 +875,6 @@ struct HostBatch {
     int run_piped()
     {
         int rc;
-        if (n_points == 0 || n_points > (1u << 24))
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "n_points must be in [1, 2^24]");
-        if (!(probe_radius >= 0.0f) || !std::isfinite(probe_radius))
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "probe_radius must be finite and >= 0");
-        for (size_t sidx = 0; sidx < n_structures; sidx++)
-            if (structure_offsets[sidx] > structure_offsets[sidx + 1])
-                return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must be non-decreasing");
-        if (structure_offsets[0] != 0) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets must span [0, n_atoms]");
         hipStream_t cp = ctx->copy_stream;
         if (!ctx->stream2) RS_HIP(ctx, new_stream(ctx, &ctx->stream2.h, 2));
         for (int attempt = 0;; attempt++) {
@@ -916,38 +904,14 @@ struct HostBatch {
     }
 };
 
-}  // namespace
-
-extern "C" {
-
-int rsasa_calculate_sasa_batch(rsasa_context_t *ctx, const float *x, const float *y,
-                               const float *z, const float *radius, const uint64_t *id,
-                               const uint32_t *structure_offsets, size_t n_structures,
-                               float probe_radius, size_t n_points, float *out_atom_sasa,
-                               const uint32_t *residue_offsets, size_t n_residues,
-                               float *out_residue_sasa)
+// rsasa_calculate_sasa_batch behind its rule, and the per-structure calls behind theirs (a single structure owns its
+// offsets {0, n_atoms}): the arguments have passed check_host_batch or check_structure_call and are not empty.
+int run_host_batch(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *radius, const uint64_t *id,
+                   const uint32_t *structure_offsets, size_t n_structures, float probe_radius, size_t n_points, float *out_atom_sasa,
+                   const uint32_t *residue_offsets, size_t n_residues, float *out_residue_sasa)
 {
-    int rc = resolve_ctx(ctx);
-    if (rc) return rc;
-    if (n_structures && !structure_offsets)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "structure_offsets is NULL");
-    const size_t N = n_structures ? structure_offsets[n_structures] : 0;
+    int rc;
     const bool want_res = residue_offsets && n_residues;
-    if (N && (!x || !y || !z || !radius))
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "coordinate / radius arrays are NULL");
-    if (want_res && !out_residue_sasa)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "out_residue_sasa is NULL");
-    if (N && !out_atom_sasa && !want_res)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "no output requested");
-    if (N == 0 && !want_res) return RSASA_OK;  // empty input -> empty output (tests/sanity.rs:149-157)
-    if (want_res) {
-        if (residue_offsets[n_residues] > N)
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "residue_offsets exceed n_atoms");
-        uint32_t decreasing = 0;  // (branch-free: vectorised; a million and a half offsets per proteome batch)
-        for (size_t k = 0; k < n_residues; k++) decreasing |= (uint32_t)(residue_offsets[k] > residue_offsets[k + 1]);
-        if (decreasing) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "residue_offsets must be non-decreasing");
-    }
-
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     RS_DEVICE(ctx);
     if (ctx->n_pending && (rc = wait_pending(ctx))) return rc;
@@ -965,6 +929,28 @@ int rsasa_calculate_sasa_batch(rsasa_context_t *ctx, const float *x, const float
     call.plan();
     if ((rc = call.stage())) return rc;
     return call.piped ? call.run_piped() : call.run_one();
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsasa_calculate_sasa_batch(rsasa_context_t *ctx, const float *x, const float *y,
+                               const float *z, const float *radius, const uint64_t *id,
+                               const uint32_t *structure_offsets, size_t n_structures,
+                               float probe_radius, size_t n_points, float *out_atom_sasa,
+                               const uint32_t *residue_offsets, size_t n_residues,
+                               float *out_residue_sasa)
+{
+    int rc = resolve_ctx(ctx);
+    if (rc) return rc;
+    bool empty;
+    if (const char *msg = check_host_batch(x, y, z, radius, structure_offsets, n_structures, probe_radius, n_points, out_atom_sasa,
+                                           residue_offsets, n_residues, out_residue_sasa, empty))
+        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, msg);
+    if (empty) return RSASA_OK;
+    return run_host_batch(ctx, x, y, z, radius, id, structure_offsets, n_structures, probe_radius, n_points, out_atom_sasa, residue_offsets,
+                          n_residues, out_residue_sasa);
 }
 
 // ---- a stream of host batches (ABI 3) ----
@@ -1131,8 +1117,10 @@ static int per_structure_call(rsasa_context_t *ctx, const SmallSource &in, size_
     if (n_atoms && !out_sasa) return RSASA_ERR_INVALID_ARGUMENT;
     int rc = resolve_ctx(ctx);
     if (rc) return rc;
-    if (n_atoms && !in.aos && (!in.x || !in.y || !in.z || !in.radius)) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "coordinate / radius arrays are NULL");
-    if (n_atoms == 0) return RSASA_OK;  // empty input -> empty output (tests/sanity.rs:149-157)
+    bool empty;
+    if (const char *msg = check_structure_call(in.aos || columns_there(in.x, in.y, in.z, in.radius), n_atoms, probe_radius, n_points, empty))
+        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, msg);
+    if (empty) return RSASA_OK;
     if (ctx->combine_wait_us.load(std::memory_order_relaxed) >= 0) {
         rc = combine_call(ctx, in, n_atoms, probe_radius, n_points, out_sasa);
         if (rc != kNotCombined) return rc;
@@ -1165,10 +1153,9 @@ static int per_structure_call(rsasa_context_t *ctx, const SmallSource &in, size_
             r[i] = in.aos[i].radius;
             ids[i] = in.aos[i].id;
         }
-        return rsasa_calculate_sasa_batch(ctx, x, y, z, r, ids.data(), offsets, 1, probe_radius, n_points, out_sasa, nullptr, 0, nullptr);
+        return run_host_batch(ctx, x, y, z, r, ids.data(), offsets, 1, probe_radius, n_points, out_sasa, nullptr, 0, nullptr);
     }
-    return rsasa_calculate_sasa_batch(ctx, in.x, in.y, in.z, in.radius, in.id, offsets, 1, probe_radius, n_points,
-                                      out_sasa, nullptr, 0, nullptr);
+    return run_host_batch(ctx, in.x, in.y, in.z, in.radius, in.id, offsets, 1, probe_radius, n_points, out_sasa, nullptr, 0, nullptr);
 }
 
 int rsasa_calculate_sasa_soa(rsasa_context_t *ctx, const float *x, const float *y,
@@ -1200,20 +1187,12 @@ int rsasa_calculate_sasa_trajectory(rsasa_context_t *ctx, const float *xyz, size
 {
     int rc = resolve_ctx(ctx);
     if (rc) return rc;
+    bool empty;
+    if (const char *msg = check_trajectory(xyz, n_frames, n_atoms, radius, probe_radius, n_points, out_atom_sasa, residue_offsets, n_residues,
+                                           out_residue_sasa, empty))
+        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, msg);
+    if (empty) return RSASA_OK;
     const bool want_res = residue_offsets && n_residues;
-    if (n_frames == 0 || n_atoms == 0) return RSASA_OK;
-    if (!xyz || !radius) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "xyz / radius are NULL");
-    if (want_res && !out_residue_sasa) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "out_residue_sasa is NULL");
-    if (!out_atom_sasa && !want_res) return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "no output requested");
-    if (n_atoms >= 0xFFFFFFF0ull || n_frames >= 0xFFFFFFF0ull || n_residues >= 0xFFFFFFF0ull)
-        return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "trajectory too large for 32-bit indices");
-    if (want_res) {
-        if (residue_offsets[n_residues] > n_atoms)
-            return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "residue_offsets exceed n_atoms");
-        for (size_t k = 0; k < n_residues; k++)
-            if (residue_offsets[k] > residue_offsets[k + 1])
-                return fail(ctx, RSASA_ERR_INVALID_ARGUMENT, "residue_offsets must be non-decreasing");
-    }
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     RS_DEVICE(ctx);
     if (ctx->n_pending && (rc = wait_pending(ctx))) return rc;
@@ -1270,7 +1249,8 @@ int rsasa_calculate_sasa_trajectory(rsasa_context_t *ctx, const float *xyz, size
         bt.n_residues = R;
         bt.out_atom_sasa = (float *)ctx->ws[0].atom_sasa.p;
         bt.out_residue_sasa = want_res ? (float *)ctx->out_res.p : nullptr;
-        if ((rc = rsasa_batch_enqueue(ctx, &bt, probe_radius, n_points, nullptr))) return rc;
+        // (frames of checked arguments: N and R fit, the offsets tile [0, N], residue sums have their output)
+        if ((rc = enqueue_checked(ctx, bt, probe_radius, n_points, nullptr))) return rc;
         if ((rc = rsasa_batch_wait(ctx))) return rc;
         if (out_atom_sasa)
             RS_HIP(ctx, hipMemcpy(out_atom_sasa + f0 * n_atoms, ctx->ws[0].atom_sasa.p, N * 4, hipMemcpyDeviceToHost));
