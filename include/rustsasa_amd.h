@@ -48,6 +48,8 @@ extern "C" {
 /* Additive under 4 as well: rsasa_dot_links, rsasa_dot_links_batch; rsasa_dot_geodesics, rsasa_dot_geodesics_batch;
  * rsasa_context_geodesic_rounds. */
 /* And: rsasa_dot_patches, rsasa_dot_patches_batch; rsasa_context_patch_stats. */
+/* And: RSASA_FIELD_PARTNER, RSASA_FIELD_MAX_CHANNELS, RSASA_FIELD_STEP, RSASA_FIELD_INV_D, RSASA_FIELD_INV_D2,
+ * RSASA_FIELD_INV_1PD, rsasa_dot_fields, rsasa_dot_fields_batch. */
 #define RSASA_ABI_VERSION 4
 
 typedef enum rsasa_status {
@@ -63,6 +65,7 @@ typedef enum rsasa_status {
                                         fewer entries than out_offsets[n] (which has been written); rsasa_group_contacts*:
                                         the same for its row buffers; rsasa_surface_components*: for out_labels;
                                         rsasa_dot_crowding*: for out_counts; rsasa_dot_enclosure*: for out_blocked;
+                                        rsasa_dot_fields*: for out_sums;
                                         rsasa_atoms_within*, rsasa_nearest_atoms*: for their out_entries;
                                         rsasa_dot_links*: for out_link_offsets and out_entries */
                                      /* rsasa_dot_patches*: for its centre and dot buffers (see there) */
@@ -813,6 +816,109 @@ int rsasa_dot_crowding_batch(rsasa_context_t *ctx,
                              uint64_t *out_dot_offsets,
                              uint32_t *out_counts, size_t counts_capacity,
                              uint32_t *out_free, float *out_atom_sasa);
+
+/* ---- dot fields --------------------------------------------------------- */
+
+/* WHAT THE CHEMISTRY looks like from each point of the accessible surface: per
+ * accessible dot and channel the sum, over the partner atoms of its structure
+ * within a cutoff, of a per-atom weight times a distance kernel - the
+ * electrostatic potential at the dot from the partial charges, the lipophilic
+ * potential from per-atom hydropathy, or a plain sum of a property within a
+ * radius: the columns that surface fingerprints, pocket scorers and interface
+ * maps put beside the shape columns.  rsasa_dot_crowding visits the same (dot,
+ * atom) pairs and adds 1; this adds weight * g(distance), up to
+ * RSASA_FIELD_MAX_CHANNELS channels in one call.
+ *
+ * The result is a 64-bit fixed-point integer per dot and channel with 24
+ * fraction bits.  A float sum would depend on the order in which the atoms are
+ * met; an integer sum does not, so the result can be checked for equality.
+ *
+ * Definition.  The dots, their order, out_dot_offsets, out_free, out_sasa, the
+ * masks and the flag byte are those of rsasa_dot_crowding: bit 0 of f_j
+ * (RSASA_FIELD_PARTNER) - the atom is a partner; the other bits are ignored;
+ * flags == NULL: every atom is a partner.  weights is float32[n][n_channels],
+ * row-major, kinds is uint8[n_channels].  All arithmetic is float32, unfused,
+ * left to right; division and square root are correctly rounded and
+ * subnormals are kept:
+ *
+ *     R_i = r_i + p;   q = c_i + R_i * s_k  (per component)      the dot (i, k), as rsasa_dot_crowding
+ *     c2  = cutoff * cutoff              (may overflow to +inf, underflow to 0)
+ *     dx  = c_j.x - q.x                  (dy, dz alike)
+ *     d2  = dx * dx + dy * dy + dz * dz;   d = sqrtf(d2)
+ *     j counts for the dot  iff  j is in the SAME structure, (f_j & 1), d2 <= c2
+ *     g[RSASA_FIELD_STEP    = 0] = 1.0f
+ *     g[RSASA_FIELD_INV_D   = 1] = 1.0f / d              Coulomb
+ *     g[RSASA_FIELD_INV_D2  = 2] = 1.0f / d2             Coulomb with a dielectric proportional to d
+ *     g[RSASA_FIELD_INV_1PD = 3] = 1.0f / (1.0f + d)     Audry's lipophilic potential
+ *     t = weights[j][c] * g[kinds[c]]
+ *     if |t| <= 0x1p24f:  out_sums[dot][c] += rint(t * 2^24)
+ *
+ * rint rounds to nearest, ties to even; t * 2^24 is exact; the sum is an int64
+ * in two's complement and wraps.  A term that is NaN or above 2^24 in magnitude
+ * adds nothing: a NaN or infinite weight, and d2 == 0 under RSASA_FIELD_INV_D
+ * and RSASA_FIELD_INV_D2 (g is +inf there; under RSASA_FIELD_INV_1PD g is 1 at
+ * d == 0 and the term counts).  A NaN d2 counts nowhere, as in rsasa_dot_crowding.  The dot's own atom
+ * is an atom like any other.  Every row is written, the all-zero ones included.
+ * The value of a field is out_sums * 2^-24.
+ *
+ * 24 fraction bits match float32 at magnitude 1; with the 2^24 bound a term
+ * takes at most 48 bits plus sign, so a sum can wrap only beyond 2^15 partners
+ * at that bound - and is defined there too, because it wraps.
+ *
+ *   out_dot_offsets  [n + 1], as rsasa_dot_crowding writes it;
+ *   out_sums         [sums_capacity][n_channels], row-major: row d is dot d,
+ *                    lined up with the rows of rsasa_dot_crowding;
+ *   out_free[i]      (nullable) the popcount of rsasa_accessible_points;
+ *   out_sasa[i]      (nullable) bit for bit rsasa_calculate_sasa_batch.
+ *
+ * Sizing, as rsasa_dot_crowding: out_dot_offsets is always written (on success
+ * and on RSASA_ERR_BUFFER_TOO_SMALL).  If out_sums is NULL or sums_capacity (in
+ * dots) < out_dot_offsets[n], nothing else is written and
+ * RSASA_ERR_BUFFER_TOO_SMALL is returned.  A batch with 2^32 or more dots
+ * returns RSASA_ERR_INVALID_ARGUMENT.
+ *
+ * n_channels must lie in [1, RSASA_FIELD_MAX_CHANNELS], every kind must be one
+ * of the four above, cutoff must be finite and >= 0 (-0.0 is 0); anything else,
+ * NULL kinds, and NULL weights where there are atoms, returns
+ * RSASA_ERR_INVALID_ARGUMENT.  The values of weights are not checked.  The
+ * remaining argument errors, the non-finite input rules, empty input, the
+ * workspace and the streams are those of rsasa_dot_crowding.  The call holds
+ * 8 * n_channels bytes per dot (and 4 * n_channels per atom) on the device; 8
+ * bytes per atom and 8 * n_channels per dot cross the link back. */
+#define RSASA_FIELD_PARTNER 1
+#define RSASA_FIELD_MAX_CHANNELS 4
+#define RSASA_FIELD_STEP 0
+#define RSASA_FIELD_INV_D 1
+#define RSASA_FIELD_INV_D2 2
+#define RSASA_FIELD_INV_1PD 3
+
+/* One structure: n_atoms atoms, id nullable (all atoms distinct).  flags:
+ * [n_atoms] or NULL; weights: [n_atoms][n_channels]; kinds: [n_channels];
+ * out_dot_offsets: [n_atoms + 1]; out_sums: [sums_capacity][n_channels];
+ * out_free, out_sasa: [n_atoms] or NULL. */
+int rsasa_dot_fields(rsasa_context_t *ctx,
+                     const float *x, const float *y, const float *z, const float *radius,
+                     const uint64_t *id, size_t n_atoms,
+                     float probe_radius, size_t n_points,
+                     const uint8_t *flags, const float *weights, const uint8_t *kinds, uint32_t n_channels,
+                     float cutoff,
+                     uint64_t *out_dot_offsets,
+                     int64_t *out_sums, size_t sums_capacity,
+                     uint32_t *out_free, float *out_sasa);
+
+/* Directory-mode form, as rsasa_dot_crowding_batch: atoms of other structures
+ * never count; flags and weights run over structure_offsets[n_structures]
+ * atoms; out_dot_offsets is batch-global. */
+int rsasa_dot_fields_batch(rsasa_context_t *ctx,
+                           const float *x, const float *y, const float *z, const float *radius,
+                           const uint64_t *id,
+                           const uint32_t *structure_offsets, size_t n_structures,
+                           float probe_radius, size_t n_points,
+                           const uint8_t *flags, const float *weights, const uint8_t *kinds, uint32_t n_channels,
+                           float cutoff,
+                           uint64_t *out_dot_offsets,
+                           int64_t *out_sums, size_t sums_capacity,
+                           uint32_t *out_free, float *out_atom_sasa);
 
 /* ---- dot enclosure ------------------------------------------------------ */
 

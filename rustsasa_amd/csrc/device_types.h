@@ -309,6 +309,23 @@ struct DcArgs {
     uint32_t *counts;                   // [dot_offsets[n_atoms]][n_bins]: every row is written
 };
 
+// ---- dot fields (fields.hip, rsasa_dot_fields*) ----
+// What DcArgs describes, with a row of weights per atom: per dot and channel the fixed-point sum of weight times a
+// distance kernel over the partner atoms of its structure within the cutoff.
+constexpr uint32_t kFieldChannels = 4;  // the channels of a call at most: a dot's accumulators are registers of k_dot_fields
+struct FdArgs {
+    PtArgs p;                           // p.masks, p.words: the masks k_accessible_points wrote; p.sasa as there
+    uint32_t *free;                     // [n_atoms] the exposed points: the popcount of the atom's mask (k_mask_free)
+    const unsigned long long *dot_offsets;  // [n_atoms + 1] exclusive scan of free: atom i's rows are [dot_offsets[i], dot_offsets[i + 1])
+    const uint8_t *sorted_flags;        // [n_atoms] HsArgs::sorted_flags (k_sort_flags): bit 0 - the atom is a partner
+    const float *weights;               // [n_atoms][n_channels], input order (read through sorted_orig)
+    uint32_t n_channels;                // 1 .. kFieldChannels
+    uint32_t kinds[kFieldChannels];     // the channels' kinds (RSASA_FIELD_*); [n_channels .. 4) are 0
+    uint32_t need;                      // bit k: some channel has kind k
+    float c2;                           // cutoff * cutoff (one float32 product; may overflow to +inf, underflow to 0)
+    long long *sums;                    // [dot_offsets[n_atoms]][n_channels]: every row is written
+};
+
 // ---- dot enclosure (enclosure.hip, rsasa_dot_enclosure*) ----
 // A finished point run (p.masks written, in input order), the grid it ran on and a flag byte per atom: the accessible
 // dots numbered as CcArgs numbers them and, per dot, the directions of a fixed fan in which the probe is stopped.
@@ -497,6 +514,8 @@ void launch_patch_sample(const PsArgs &ps, hipStream_t stream);
 void launch_patch_pack(const PsArgs &ps, hipStream_t stream);
 // The rows of the dots (crowding.hip) from those masks and counts, with DcArgs::dot_offsets and ::sorted_flags.
 void launch_dot_crowding(const DcArgs &d, hipStream_t stream);
+// The fixed-point sums of the dots (fields.hip) from the same, with FdArgs::weights in input order.
+void launch_dot_fields(const FdArgs &d, hipStream_t stream);
 // The blocked directions of the dots (enclosure.hip) from those masks and counts, with DeArgs::dot_offsets and ::sorted_flags.
 void launch_dot_enclosure(const DeArgs &d, hipStream_t stream);
 // The half-sphere counts (hse.hip) on a binned batch: the flags in cell-sorted order, then up[] and down[].

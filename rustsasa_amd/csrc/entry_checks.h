@@ -203,6 +203,20 @@ inline const char *check_crowding(const float *edges, uint32_t n_bins)
     return check_edges(edges, n_bins);
 }
 
+// The channels of the dot fields: 1 .. RSASA_FIELD_MAX_CHANNELS kinds, each one of RSASA_FIELD_STEP .. _INV_1PD - a
+// dot's accumulators are registers of k_dot_fields - and a cutoff that is finite and not negative (-0.0 is 0).  The
+// weights' values have no rule.
+constexpr uint32_t kFieldMaxChannels = 4, kFieldKinds = 4;
+inline const char *check_fields(const uint8_t *kinds, uint32_t n_channels, float cutoff)
+{
+    if (n_channels < 1u || n_channels > kFieldMaxChannels) return "n_channels must be in [1, 4]";
+    if (!kinds) return "NULL argument";
+    for (uint32_t c = 0; c < n_channels; c++)
+        if (kinds[c] >= kFieldKinds) return "kinds must be RSASA_FIELD_STEP, _INV_D, _INV_D2 or _INV_1PD";
+    if (!(cutoff >= 0.0f) || std::isinf(cutoff)) return "cutoff must be finite and not negative";
+    return nullptr;
+}
+
 // The fan of the dot enclosure: 1 .. RSASA_ENCLOSE_MAX_DIRS directions - a dot's word of k_dot_enclosure has a bit for
 // each - and a reach that is finite and not negative (-0.0 is 0).
 constexpr uint32_t kEncloseMaxDirs = 32;

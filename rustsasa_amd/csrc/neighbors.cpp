@@ -1,11 +1,11 @@
-// Host side of the seventeen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
+// Host side of the eighteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
 // batch pair of include/rustsasa_amd.h: the neighbour lists (rsasa_precompute_neighbors*); the point runs built on
 // them - accessible points, exposure vectors, atom depth, surface components, dot links, dot geodesics, dot patches, dot crowding,
-// dot enclosure, contact counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
+// dot fields, dot enclosure, contact counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
 // atoms, radial counts.  The grid is built by the SASA path's kernels (nb_grid, and hs_grid for the runs on the grid
 // alone), then neighbors.hip counts, scans and fills the lists (nb_count, nb_fill).  A point run keeps the lists on the
 // device: every family shares one prologue (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and
-// adds its own kernels of points.hip, depth.hip, components.hip, geodesics.hip, patches.hip, crowding.hip or enclosure.hip and its
+// adds its own kernels of points.hip, depth.hip, components.hip, geodesics.hip, patches.hip, crowding.hip, fields.hip or enclosure.hip and its
 // own downloads.
 // Every family is one function (*_run) behind its two entry points, which only forward to it: the single form as
 // Form::one(n_atoms), the batch form as Form::many(structure_offsets, n_structures).  The function opens with the rules
@@ -814,6 +814,58 @@ int dc_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     return RSASA_OK;
 }
 
+// ---- dot fields (rsasa_dot_fields*) ----
+
+// One run of the dot fields: dc_run's dots and sorted flags, with the weight rows uploaded beside them in input order;
+// the caller's buffer is checked against out_offsets[N], then k_dot_fields fills a row of n_channels sums per dot.  8
+// bytes per atom and 8 * n_channels per dot come back (and 4 per atom each for the counts and the values, if asked).
+int fd_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id, Form form,
+           float probe, size_t n_points, const uint8_t *flags, const float *weights, const uint8_t *kinds, uint32_t n_channels,
+           float cutoff, uint64_t *out_offsets, int64_t *out_sums, size_t cap, uint32_t *out_free, float *out_sasa)
+{
+    static_assert(kFieldMaxChannels == RSASA_FIELD_MAX_CHANNELS && kFieldMaxChannels == kFieldChannels,
+                  "the header's bound is the kernel's bound");
+    static_assert(RSASA_FIELD_STEP == 0 && RSASA_FIELD_INV_D == 1 && RSASA_FIELD_INV_D2 == 2 && RSASA_FIELD_INV_1PD == 3 &&
+                      kFieldKinds == 4, "the kinds as k_dot_fields reads them");
+    static_assert(sizeof(long long) == sizeof(int64_t), "a sum is 64 bits");
+    Cols c(x, y, z, r, id);
+    if (int rc = entry_open(ctx, c, form, &n_points, out_offsets, weights != nullptr)) return rc;
+    RS_ARGS(ctx, check_fields(kinds, n_channels, cutoff));
+    Run f(ctx);
+    if (!f.open(c.N, out_offsets)) return f.rc;
+    int rc;
+    Lists l;
+    FdArgs fd{};
+    HsArgs h{};
+    if ((rc = pt_count(f, c, probe, nullptr, l)) || (rc = pt_prepare(f, l, n_points, true, out_sasa != nullptr, fd.p)) ||
+        (rc = f.reserve(f.R.free, c.N * 4, fd.free)) || (rc = f.reserve(f.R.row_offsets, (c.N + 1) * 8, fd.dot_offsets)) ||
+        (rc = hs_flags(f, c.N, flags, h)) || (rc = f.upload(f.R.field_w, weights, c.N * n_channels * 4, fd.weights)))
+        return rc;
+    h.b = fd.p.b;
+    fd.sorted_flags = h.sorted_flags;
+    fd.n_channels = n_channels;
+    for (uint32_t k = 0; k < n_channels; k++) {
+        fd.kinds[k] = kinds[k];
+        fd.need |= 1u << kinds[k];
+    }
+    const float cut = cutoff + 0.0f;  // (-0.0 is 0)
+    fd.c2 = cut * cut;
+    uint64_t n_dots;
+    if ((rc = pt_dots(f, l, fd.p, fd.free, &h, out_offsets, n_dots))) return rc;
+    if (!out_sums || cap < n_dots)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL, "out_sums is NULL or holds fewer rows than out_dot_offsets[n]");
+    if (n_dots) {
+        if ((rc = f.reserve(f.R.fields, n_dots * n_channels * 8, fd.sums))) return rc;
+        launch_dot_fields(fd, f.st);
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, download(out_sums, fd.sums, n_dots * n_channels * 8, f.st));
+    }
+    RS_HIP(ctx, download(out_free, fd.free, c.N * 4, f.st));
+    RS_HIP(ctx, download(out_sasa, fd.p.sasa, c.N * 4, f.st));
+    RS_HIP(ctx, hipStreamSynchronize(f.st));
+    return RSASA_OK;
+}
+
 // ---- dot enclosure (rsasa_dot_enclosure*) ----
 
 // One run of the dot enclosure: dc_run's dots and sorted flags; the fan of n_dirs directions is computed here
@@ -1335,6 +1387,25 @@ int rsasa_dot_crowding_batch(rsasa_context_t *ctx, const float *x, const float *
 {
     return dc_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, flags, edges,
                     n_bins, out_dot_offsets, out_counts, counts_capacity, out_free, out_atom_sasa);
+}
+
+int rsasa_dot_fields(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                     const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, const uint8_t *flags,
+                     const float *weights, const uint8_t *kinds, uint32_t n_channels, float cutoff, uint64_t *out_dot_offsets,
+                     int64_t *out_sums, size_t sums_capacity, uint32_t *out_free, float *out_sasa)
+{
+    return fd_run(ctx, x, y, z, radius, id, Form::one(n_atoms), probe_radius, n_points, flags, weights, kinds, n_channels,
+                    cutoff, out_dot_offsets, out_sums, sums_capacity, out_free, out_sasa);
+}
+
+int rsasa_dot_fields_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                           const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                           size_t n_points, const uint8_t *flags, const float *weights, const uint8_t *kinds,
+                           uint32_t n_channels, float cutoff, uint64_t *out_dot_offsets, int64_t *out_sums,
+                           size_t sums_capacity, uint32_t *out_free, float *out_atom_sasa)
+{
+    return fd_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, flags, weights,
+                    kinds, n_channels, cutoff, out_dot_offsets, out_sums, sums_capacity, out_free, out_atom_sasa);
 }
 
 int rsasa_dot_enclosure(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,

@@ -12,7 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import (ATOM_DTYPE, CROWD_MAX_BINS, ENCLOSE_MAX_DIRS, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS,
+from ._capi import (ATOM_DTYPE, CROWD_MAX_BINS, ENCLOSE_MAX_DIRS, FIELD_MAX_CHANNELS, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS,
                     RADIAL_MAX_CLASSES, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings, check,
                     ptr)
 
@@ -576,6 +576,51 @@ class Context:
         count); dot_offsets and the rows run over the whole batch."""
         return self._dot_crowding(x, y, z, radius, ids, probe_radius, n_points, edges, flags, structure_offsets)
 
+    # ---- dot fields (weighted sums of atom properties around each accessible dot: potentials on the surface) ----
+    def _dot_fields(self, x, y, z, radius, ids, probe_radius, n_points, weights, kinds, cutoff, flags, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("dot_fields", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        flags = _flag_bytes(flags, n)
+        if weights is None:
+            raise ValueError("weights must be an array of one row per atom")
+        weights = _f32(weights)
+        if weights.ndim == 1:
+            weights = np.ascontiguousarray(weights[:, None])
+        if weights.ndim != 2 or weights.shape[0] != n or not 1 <= weights.shape[1] <= FIELD_MAX_CHANNELS:
+            raise ValueError(f"weights must be an array of shape ({n},) or ({n}, C) with 1 <= C <= {FIELD_MAX_CHANNELS}")
+        n_channels = weights.shape[1]
+        k = np.full(n_channels, FIELD_INV_D, np.int64) if kinds is None else np.atleast_1d(np.asarray(kinds))
+        if k.dtype.kind not in "ui" or k.shape != (n_channels,) or (k.size and (int(k.min()) < 0 or int(k.max()) > 0xFF)):
+            raise ValueError(f"kinds must be {n_channels} integers (one FIELD_* kind per channel of weights)")
+        k = np.ascontiguousarray(k, dtype=np.uint8)
+        free, sasa = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+
+        def call(offsets, sums, cap):
+            return entry(probe_radius, n_points, ptr(flags), ptr(weights), ptr(k), n_channels, cutoff, ptr(offsets), ptr(sums),
+                         cap, ptr(free), ptr(sasa))
+        return self._sized_call(call, n, min(n_points, 16) * n, np.dtype((np.int64, (n_channels,)))) + (free, sasa)
+
+    def dot_fields(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, weights=None, kinds=None,
+                   cutoff: float = 10.0, flags=None):
+        """rsasa_dot_fields: (dot_offsets uint64[N + 1], sums int64[D, C], free uint32[N], sasa float32[N]).  The rows of
+        sums are the accessible dots in the order of surface_points() and of dot_crowding's rows.  sums[d, c] is the sum
+        over the atoms j with FIELD_PARTNER in flags[j] - the dot's own atom included - whose float32 d2 to the dot is at
+        most cutoff * cutoff, of rint(weights[j, c] * g * 2^24), where g is 1 (FIELD_STEP), 1 / d (FIELD_INV_D: Coulomb),
+        1 / d2 (FIELD_INV_D2) or 1 / (1 + d) (FIELD_INV_1PD: the lipophilic potential) as kinds[c] says, evaluated as the
+        header defines it in plain float32; a term that is NaN or above 2^24 in magnitude adds nothing.  The sums are
+        integers and wrap, so they have no order and can be checked for equality; field_values() turns them into float64.
+        weights: float32[N] (one channel) or [N, C] with C up to FIELD_MAX_CHANNELS; kinds None: every channel FIELD_INV_D;
+        cutoff finite and not negative; flags None: every atom is a partner.  dot_means() averages a column over the
+        atoms.  free is the popcount of accessible_points, sasa equals calculate_sasa_soa."""
+        return self._dot_fields(x, y, z, radius, ids, probe_radius, n_points, weights, kinds, cutoff, flags)
+
+    def dot_fields_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100,
+                         weights=None, kinds=None, cutoff: float = 10.0, flags=None):
+        """rsasa_dot_fields_batch: dot_fields of every structure (one grid each, atoms of other structures never count);
+        dot_offsets and the rows run over the whole batch."""
+        return self._dot_fields(x, y, z, radius, ids, probe_radius, n_points, weights, kinds, cutoff, flags, structure_offsets)
+
     # ---- dot enclosure (in which directions a probe leaving an accessible dot is stopped by protein) ----
     def _dot_enclosure(self, x, y, z, radius, ids, probe_radius, n_points, n_dirs, reach, flags, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -1021,6 +1066,19 @@ CROWD_PARTNER = 1  # flag bit of dot_crowding: the atom is counted
 
 
 ENCLOSE_PARTNER = 1  # flag bit of dot_enclosure: the atom is an obstacle
+
+
+FIELD_PARTNER = 1  # flag bit of dot_fields: the atom contributes
+FIELD_STEP, FIELD_INV_D, FIELD_INV_D2, FIELD_INV_1PD = 0, 1, 2, 3  # the distance kernels of dot_fields: 1, 1 / d, 1 / d2, 1 / (1 + d)
+FIELD_FRACTION_BITS = 24  # the sums of dot_fields are fixed point: value = sum * 2^-24
+
+
+def field_values(sums) -> np.ndarray:
+    """float64, the shape of sums: the fields of dot_fields[_batch] as numbers, sums * 2^-24 (exact up to 2^53)."""
+    s = np.asarray(sums)
+    if s.dtype != np.int64:
+        raise ValueError("sums must be the int64 array dot_fields returns")
+    return s.astype(np.float64) * 2.0 ** -FIELD_FRACTION_BITS
 
 
 def _blocked_bits(blocked, n_dirs):
