@@ -43,6 +43,7 @@ RADIAL_MAX_CLASSES = 16  # RSASA_RADIAL_MAX_CLASSES, RSASA_RADIAL_MAX_BINS: the 
 RADIAL_MAX_BINS = 32
 CROWD_MAX_BINS = 8  # RSASA_CROWD_MAX_BINS: the widest row of rsasa_dot_crowding*
 FIELD_MAX_CHANNELS = 4  # RSASA_FIELD_MAX_CHANNELS: the most channels of rsasa_dot_fields*
+CURV_COLUMNS = 8  # RSASA_CURV_COLUMNS: the moments per dot of rsasa_dot_curvature*
 ENCLOSE_MAX_DIRS = 32  # RSASA_ENCLOSE_MAX_DIRS: the most directions of rsasa_dot_enclosure*
 
 
@@ -141,6 +142,10 @@ SYMBOLS = {
                                    C.c_float, _vp, _vp, C.c_size_t, _vp, _vp]),
     "rsasa_dot_fields_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, _vp, _vp, _vp,
                                          C.c_uint32, C.c_float, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "rsasa_dot_curvature": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, C.c_float, _vp, _vp, _vp,
+                                      C.c_size_t, _vp, _vp]),
+    "rsasa_dot_curvature_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, C.c_float, _vp,
+                                            _vp, _vp, C.c_size_t, _vp, _vp]),
     "rsasa_dot_enclosure": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, _vp, C.c_float,
                                       C.c_uint32, _vp, _vp, C.c_size_t, _vp, _vp]),
     "rsasa_dot_enclosure_batch": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.c_float, C.c_size_t, _vp,

@@ -270,6 +270,16 @@ struct GdArgs {
     uint32_t *flags;                    // [kGdRounds] nonzero: that round of the current group lowered a value
 };
 
+// ---- dot curvature (curvature.hip, rsasa_dot_curvature*) ----
+// The dots and the hit test of CcArgs with the reach as its link (c.parent and c.labels unused): per dot the number of
+// dots of its structure within the reach and eight fixed-point sums over them.
+constexpr uint32_t kCurvColumns = 8;    // RSASA_CURV_D2 .. RSASA_CURV_YZ: the columns of a row of moments
+struct CvArgs {
+    CcArgs c;                           // c.p.masks, c.free, c.dot_offsets, c.n_dots; c.link = reach, c.link2 = reach * reach
+    uint32_t *pairs;                    // [n_dots] the pairs that count per dot (zeroed by the caller)
+    unsigned long long *moments;        // [n_dots][kCurvColumns] the wrapping sums, 24 fraction bits (zeroed by the caller)
+};
+
 // ---- dot patches (patches.hip, rsasa_dot_patches*) ----
 // The lists of the geodesics (g.raw as weights) and their dist, stamp and source: per structure the farthest-point
 // sample of its dots along the graph, one workgroup of k_patch_sample per structure.
@@ -512,6 +522,8 @@ void launch_geodesic_restamp(const GdArgs &gd, hipStream_t stream);
 void launch_patch_sample(const PsArgs &ps, hipStream_t stream);
 // The centres and covers of the sample moved together (patches.hip): ps.centre_offsets -> ps.packed_centres, ps.packed_cover.
 void launch_patch_pack(const PsArgs &ps, hipStream_t stream);
+// The pair counts and moments of the dots (curvature.hip) from those masks and counts; the caller has zeroed both.
+void launch_dot_curvature(const CvArgs &cv, hipStream_t stream);
 // The rows of the dots (crowding.hip) from those masks and counts, with DcArgs::dot_offsets and ::sorted_flags.
 void launch_dot_crowding(const DcArgs &d, hipStream_t stream);
 // The fixed-point sums of the dots (fields.hip) from the same, with FdArgs::weights in input order.

@@ -444,8 +444,8 @@ struct rsasa_context {
     size_t stream_sub_batches = 0; // a worker context of a stream of host batches: most sub-batches of a call (0: the default)
     struct HostStream *host_stream = nullptr;  // rsasa_host_batch_enqueue / _wait: two workers with a context each
     std::atomic<int> combine_wait_us{-1};      // rsasa_context_set_call_combining: -1 off, else how long a leader may hold a batch back for company
-    // The eighteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
-    // exposure vectors, atom depth, surface components, dot links, dot geodesics, dot patches, dot crowding, dot fields, dot enclosure, contact
+    // The nineteen families of neighbors.cpp: rsasa_precompute_neighbors*; the point runs behind them - accessible points,
+    // exposure vectors, atom depth, surface components, dot links, dot geodesics, dot patches, dot crowding, dot fields, dot curvature, dot enclosure, contact
     // counts, contact owners, group contacts; and
     // the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest atoms, radial counts.  A
     // workspace of their own: device batches in flight in ws[0] / ws[1] are neither waited for nor disturbed; the calls
@@ -483,6 +483,7 @@ struct rsasa_context {
         DeviceBuffer classes, so, table, pairs;
         DeviceBuffer crowd;  // dot crowding: a row of n_bins counts per dot (DcArgs::counts)
         DeviceBuffer field_w, fields;  // dot fields: the weight rows per atom (FdArgs::weights); a row of n_channels sums per dot (::sums)
+        DeviceBuffer curv_pairs, curv_moments;  // dot curvature: a pair count and a row of eight sums per dot (CvArgs::pairs, ::moments)
         DeviceBuffer enclose;  // dot enclosure: a word of blocked directions per dot (DeArgs::blocked)
         // dot links and geodesics (GdArgs): per dot the counts, cursors and link offsets; per entry the lists in sweep order
         // and sorted; per dot the seed bytes, dist, stamp and source; the rounds' flags

@@ -217,6 +217,13 @@ inline const char *check_fields(const uint8_t *kinds, uint32_t n_channels, float
     return nullptr;
 }
 
+// The reach of the dot curvature: finite and not negative (-0.0 is 0; 0 is legal and gives zero rows).
+inline const char *check_curvature(float reach)
+{
+    if (!(reach >= 0.0f) || std::isinf(reach)) return "reach must be finite and not negative";
+    return nullptr;
+}
+
 // The fan of the dot enclosure: 1 .. RSASA_ENCLOSE_MAX_DIRS directions - a dot's word of k_dot_enclosure has a bit for
 // each - and a reach that is finite and not negative (-0.0 is 0).
 constexpr uint32_t kEncloseMaxDirs = 32;

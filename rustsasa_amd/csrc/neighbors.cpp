@@ -1,11 +1,11 @@
-// Host side of the eighteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
+// Host side of the nineteen families that run on a grid of the context's own (rsasa_context::nb_ws), each a single /
 // batch pair of include/rustsasa_amd.h: the neighbour lists (rsasa_precompute_neighbors*); the point runs built on
 // them - accessible points, exposure vectors, atom depth, surface components, dot links, dot geodesics, dot patches, dot crowding,
-// dot fields, dot enclosure, contact counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
+// dot fields, dot curvature, dot enclosure, contact counts, contact owners, group contacts; and the runs on the grid alone - half-sphere exposure, atoms within a cutoff, the k nearest
 // atoms, radial counts.  The grid is built by the SASA path's kernels (nb_grid, and hs_grid for the runs on the grid
 // alone), then neighbors.hip counts, scans and fills the lists (nb_count, nb_fill).  A point run keeps the lists on the
 // device: every family shares one prologue (pt_count, pt_prepare: lists with the SASA path's cutoff, lattice, PtArgs) and
-// adds its own kernels of points.hip, depth.hip, components.hip, geodesics.hip, patches.hip, crowding.hip, fields.hip or enclosure.hip and its
+// adds its own kernels of points.hip, depth.hip, components.hip, geodesics.hip, patches.hip, crowding.hip, fields.hip, curvature.hip or enclosure.hip and its
 // own downloads.
 // Every family is one function (*_run) behind its two entry points, which only forward to it: the single form as
 // Form::one(n_atoms), the batch form as Form::many(structure_offsets, n_structures).  The function opens with the rules
@@ -866,6 +866,57 @@ int fd_run(rsasa_context *ctx, const float *x, const float *y, const float *z, c
     return RSASA_OK;
 }
 
+// ---- dot curvature (rsasa_dot_curvature*) ----
+
+// One run of the dot curvature: the dots as in cc_run with the reach as their link; the caller's two buffers are checked
+// against out_offsets[N], both device buffers are zeroed (k_dot_curvature adds to its rows), then the kernel fills a pair
+// count and a row of eight sums per dot.  8 bytes per atom and 68 per dot come back (and 4 per atom each for the counts
+// and the values, if asked).
+int cv_run(rsasa_context *ctx, const float *x, const float *y, const float *z, const float *r, const uint64_t *id, Form form,
+           float probe, size_t n_points, float reach, uint64_t *out_offsets, uint32_t *out_pairs, int64_t *out_moments, size_t cap,
+           uint32_t *out_free, float *out_sasa)
+{
+    static_assert(RSASA_CURV_D2 == 0 && RSASA_CURV_H == 1 && RSASA_CURV_XX == 2 && RSASA_CURV_YY == 3 && RSASA_CURV_ZZ == 4 &&
+                      RSASA_CURV_XY == 5 && RSASA_CURV_XZ == 6 && RSASA_CURV_YZ == 7 && RSASA_CURV_COLUMNS == kCurvColumns,
+                  "the columns as k_dot_curvature writes them");
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "a sum is 64 bits");
+    Cols c(x, y, z, r, id);
+    if (int rc = entry_open(ctx, c, form, &n_points, out_offsets, true)) return rc;
+    RS_ARGS(ctx, check_curvature(reach));
+    Run f(ctx);
+    if (!f.open(c.N, out_offsets)) return f.rc;
+    int rc;
+    Lists l;
+    CvArgs cv{};
+    CcArgs &cc = cv.c;
+    if ((rc = pt_count(f, c, probe, nullptr, l)) || (rc = pt_prepare(f, l, n_points, true, out_sasa != nullptr, cc.p)) ||
+        (rc = f.reserve(f.R.free, c.N * 4, cc.free)) || (rc = f.reserve(f.R.row_offsets, (c.N + 1) * 8, cc.dot_offsets)))
+        return rc;
+    cc.link = reach + 0.0f;  // (-0.0 is 0)
+    cc.link2 = cc.link * cc.link;
+    uint64_t n_dots;
+    if ((rc = pt_dots(f, l, cc.p, cc.free, nullptr, out_offsets, n_dots))) return rc;
+    if (!out_pairs || !out_moments || cap < n_dots)
+        return fail(ctx, RSASA_ERR_BUFFER_TOO_SMALL,
+                    "out_pairs or out_moments is NULL or holds fewer dots than out_dot_offsets[n]");
+    if (n_dots) {
+        if ((rc = f.reserve(f.R.curv_pairs, n_dots * 4, cv.pairs)) ||
+            (rc = f.reserve(f.R.curv_moments, n_dots * kCurvColumns * 8, cv.moments)))
+            return rc;
+        cc.n_dots = n_dots;
+        RS_HIP(ctx, hipMemsetAsync(cv.pairs, 0, n_dots * 4, f.st));
+        RS_HIP(ctx, hipMemsetAsync(cv.moments, 0, n_dots * kCurvColumns * 8, f.st));
+        launch_dot_curvature(cv, f.st);
+        RS_HIP(ctx, hipGetLastError());
+        RS_HIP(ctx, download(out_pairs, cv.pairs, n_dots * 4, f.st));
+        RS_HIP(ctx, download(out_moments, cv.moments, n_dots * kCurvColumns * 8, f.st));
+    }
+    RS_HIP(ctx, download(out_free, cc.free, c.N * 4, f.st));
+    RS_HIP(ctx, download(out_sasa, cc.p.sasa, c.N * 4, f.st));
+    RS_HIP(ctx, hipStreamSynchronize(f.st));
+    return RSASA_OK;
+}
+
 // ---- dot enclosure (rsasa_dot_enclosure*) ----
 
 // One run of the dot enclosure: dc_run's dots and sorted flags; the fan of n_dirs directions is computed here
@@ -1406,6 +1457,24 @@ int rsasa_dot_fields_batch(rsasa_context_t *ctx, const float *x, const float *y,
 {
     return fd_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, flags, weights,
                     kinds, n_channels, cutoff, out_dot_offsets, out_sums, sums_capacity, out_free, out_atom_sasa);
+}
+
+int rsasa_dot_curvature(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                        const uint64_t *id, size_t n_atoms, float probe_radius, size_t n_points, float reach,
+                        uint64_t *out_dot_offsets, uint32_t *out_pairs, int64_t *out_moments, size_t dots_capacity,
+                        uint32_t *out_free, float *out_sasa)
+{
+    return cv_run(ctx, x, y, z, radius, id, Form::one(n_atoms), probe_radius, n_points, reach, out_dot_offsets, out_pairs,
+                  out_moments, dots_capacity, out_free, out_sasa);
+}
+
+int rsasa_dot_curvature_batch(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,
+                              const uint64_t *id, const uint32_t *structure_offsets, size_t n_structures, float probe_radius,
+                              size_t n_points, float reach, uint64_t *out_dot_offsets, uint32_t *out_pairs,
+                              int64_t *out_moments, size_t dots_capacity, uint32_t *out_free, float *out_atom_sasa)
+{
+    return cv_run(ctx, x, y, z, radius, id, Form::many(structure_offsets, n_structures), probe_radius, n_points, reach,
+                  out_dot_offsets, out_pairs, out_moments, dots_capacity, out_free, out_atom_sasa);
 }
 
 int rsasa_dot_enclosure(rsasa_context_t *ctx, const float *x, const float *y, const float *z, const float *radius,

@@ -12,7 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from ._capi import (ATOM_DTYPE, CROWD_MAX_BINS, ENCLOSE_MAX_DIRS, FIELD_MAX_CHANNELS, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS,
+from ._capi import (ATOM_DTYPE, CROWD_MAX_BINS, CURV_COLUMNS, ENCLOSE_MAX_DIRS, FIELD_MAX_CHANNELS, NEAREST_MAX_K, NEIGHBOR_DTYPE, RADIAL_MAX_BINS,
                     RADIAL_MAX_CLASSES, WITHIN_CENTRE, WITHIN_DTYPE, WITHIN_PARTNER, DeviceBatch, RsasaError, Timings, check,
                     ptr)
 
@@ -621,6 +621,37 @@ class Context:
         dot_offsets and the rows run over the whole batch."""
         return self._dot_fields(x, y, z, radius, ids, probe_radius, n_points, weights, kinds, cutoff, flags, structure_offsets)
 
+    # ---- dot curvature (the moments of the dots around each accessible dot: mean and principal curvatures, shape index) ----
+    def _dot_curvature(self, x, y, z, radius, ids, probe_radius, n_points, reach, structure_offsets=_SINGLE):
+        n_points = _n_points(n_points)
+        (x, *_), entry = self._entry("dot_curvature", x, y, z, radius, ids, structure_offsets)
+        n = x.shape[0]
+        free, sasa = np.zeros(n, np.uint32), np.zeros(n, np.float32)
+
+        def call(offsets, pairs, moments, cap):
+            return entry(probe_radius, n_points, reach, ptr(offsets), ptr(pairs), ptr(moments), cap, ptr(free), ptr(sasa))
+        return self._sized_call(call, n, min(n_points, 16) * n, np.dtype(np.uint32), np.dtype((np.int64, (CURV_COLUMNS,)))) + (free, sasa)
+
+    def dot_curvature(self, x, y, z, radius, ids=None, probe_radius: float = 1.4, n_points: int = 100, reach: float = 3.0):
+        """rsasa_dot_curvature: (dot_offsets uint64[N + 1], pairs uint32[D], moments int64[D, 8], free uint32[N], sasa
+        float32[N]).  The rows are the accessible dots in the order of surface_points().  For dot a with normal n (its
+        lattice point) and every other dot b of its structure with float32 d2 <= reach * reach, the header's plain float32
+        h = n . (q_b - q_a), t = (q_b - q_a) - h n, g = h / |t|^2 give the terms d2, h and (t t^t) g (CURV_D2, CURV_H,
+        CURV_XX .. CURV_YZ); a pair counts - 1 to pairs[a], rint(term * 2^24) to each column of moments[a] - iff d2 > 0,
+        |t|^2 > 0 and every |term| <= 2^24, for all columns or for none.  The sums are integers and wrap, so rows can be
+        checked for equality; curvature_values() turns them into mean, Gaussian and principal curvatures and the shape
+        index.  The mean is robust at any density; the principal split wants about 50 pairs or more per dot (on a lone
+        sphere at 100 points and reach 3, k1 R ranges over 1.02 .. 1.41), and dots at the rim of the accessible surface
+        see a half-disc.  reach finite and not negative; 0 gives zero rows.  dot_means() averages a column over the
+        atoms.  free is the popcount of accessible_points, sasa equals calculate_sasa_soa."""
+        return self._dot_curvature(x, y, z, radius, ids, probe_radius, n_points, reach)
+
+    def dot_curvature_batch(self, x, y, z, radius, ids, structure_offsets, probe_radius: float = 1.4, n_points: int = 100,
+                            reach: float = 3.0):
+        """rsasa_dot_curvature_batch: dot_curvature of every structure (one grid each, dots of different structures never
+        pair); dot_offsets and the rows run over the whole batch."""
+        return self._dot_curvature(x, y, z, radius, ids, probe_radius, n_points, reach, structure_offsets)
+
     # ---- dot enclosure (in which directions a probe leaving an accessible dot is stopped by protein) ----
     def _dot_enclosure(self, x, y, z, radius, ids, probe_radius, n_points, n_dirs, reach, flags, structure_offsets=_SINGLE):
         n_points = _n_points(n_points)
@@ -1079,6 +1110,70 @@ def field_values(sums) -> np.ndarray:
     if s.dtype != np.int64:
         raise ValueError("sums must be the int64 array dot_fields returns")
     return s.astype(np.float64) * 2.0 ** -FIELD_FRACTION_BITS
+
+
+CURV_D2, CURV_H, CURV_XX, CURV_YY, CURV_ZZ, CURV_XY, CURV_XZ, CURV_YZ = range(8)  # the columns of dot_curvature's moments
+
+
+def curvature_values(pairs, moments, directions=False, normals=None):
+    """float64[D] each: (mean, gaussian, k1, k2, shape_index) of the rows dot_curvature[_batch] returns.
+    mean = -2 Sum(h) / Sum(d2), the least-squares normal curvature (positive on convex surface).  The six moment columns
+    give Taubin's tensor M = -2 Sum(h T T^t) / Sum(d2); its tangential eigenvalues m1 >= m2 follow from the trace and the
+    Frobenius norm alone, (tr M +- sqrt(2 |M|_F^2 - tr^2)) / 2, and k1 = 3 m1 - m2 >= k2 = 3 m2 - m1 are the principal
+    curvatures (k1 + k2 = 2 tr M); gaussian = k1 k2; shape_index = (2 / pi) atan2(k1 + k2, k1 - k2): +1 a convex cap, 0 a
+    saddle, -1 a cup.  All NaN where pairs == 0 or Sum(d2) == 0.  The mean is robust at any density; the split of k1 and
+    k2 wants about 50 pairs or more (see dot_curvature).
+    directions=True: two more results, float64[D, 3] each - the unit principal directions of k1 and k2 (sign free).  With
+    normals (float[D, 3]: the dots' outward normals, which are their lattice points - sphere_points(n_points)[k] of the
+    accessible points in dot order, or (q - c) / (r + probe) from surface_points) the tensor is restricted to the plane
+    orthogonal to each normal and numpy.linalg.eigh solves the 2 x 2 problem there: the directions are tangential
+    whatever the curvatures.  Without them eigh runs on the 3 x 3 tensor and, of its three eigenvectors, the one whose
+    eigenvalue is smallest in magnitude is taken for the normal (M n ~ 0): where m1 or m2 is itself near 0 - flat or
+    parabolic dots - that choice is not determined, and a returned direction can be the normal; pass normals there."""
+    p, s = np.asarray(pairs), np.asarray(moments)
+    if s.dtype != np.int64 or s.ndim != 2 or s.shape[1] != CURV_COLUMNS or p.shape != s.shape[:1]:
+        raise ValueError("pairs and moments must be the uint32[D] and int64[D, 8] arrays dot_curvature returns")
+    ok = (p != 0) & (s[:, CURV_D2] != 0)
+    v = s.astype(np.float64)          # (the scale 2^-24 cancels in every ratio)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w = np.where(ok, -2.0 / v[:, CURV_D2], np.nan)
+        mean = w * v[:, CURV_H]
+        m = w[:, None] * v[:, CURV_XX:]
+        tr = m[:, 0] + m[:, 1] + m[:, 2]
+        fro2 = m[:, 0] ** 2 + m[:, 1] ** 2 + m[:, 2] ** 2 + 2.0 * (m[:, 3] ** 2 + m[:, 4] ** 2 + m[:, 5] ** 2)
+        root = np.sqrt(np.maximum(2.0 * fro2 - tr * tr, 0.0))
+        m1, m2 = (tr + root) / 2.0, (tr - root) / 2.0
+        k1, k2 = 3.0 * m1 - m2, 3.0 * m2 - m1
+        out = (mean, k1 * k2, k1, k2, (2.0 / np.pi) * np.arctan2(k1 + k2, k1 - k2))
+    if not directions:
+        return out
+    d1, d2 = np.full((len(p), 3), np.nan), np.full((len(p), 3), np.nan)
+    rows = np.flatnonzero(ok)
+    if normals is not None:
+        nrm = np.asarray(normals, np.float64)
+        if nrm.shape != (len(p), 3):
+            raise ValueError(f"normals must be an array of shape ({len(p)}, 3): one outward normal per dot")
+    if len(rows):
+        t = np.empty((len(rows), 3, 3))
+        for (i, j), c in zip(((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2)), range(6)):
+            t[:, i, j] = t[:, j, i] = m[rows, c]
+        at = np.arange(len(rows))
+        if normals is None:
+            val, vec = np.linalg.eigh(t)                               # ascending eigenvalues, unit eigenvectors in columns
+            normal = np.argmin(np.abs(val), axis=1)
+            keep = np.array([[1, 2], [0, 2], [0, 1]])[normal]          # the other two, ascending: (m2, m1)
+            d1[rows], d2[rows] = vec[at, :, keep[:, 1]], vec[at, :, keep[:, 0]]
+        else:
+            n = nrm[rows] / np.linalg.norm(nrm[rows], axis=1, keepdims=True)
+            axis = np.eye(3)[np.argmin(np.abs(n), axis=1)]             # the coordinate axis least along the normal
+            e1 = np.cross(n, axis)
+            e1 /= np.linalg.norm(e1, axis=1, keepdims=True)
+            e2 = np.cross(n, e1)
+            basis = np.stack([e1, e2], -1)                             # [rows, 3, 2]: an orthonormal basis of the tangent plane
+            val, vec = np.linalg.eigh(np.swapaxes(basis, 1, 2) @ t @ basis)
+            d1[rows] = (basis @ vec[:, :, 1:2])[:, :, 0]               # ascending: column 1 belongs to m1, column 0 to m2
+            d2[rows] = (basis @ vec[:, :, 0:1])[:, :, 0]
+    return out + (d1, d2)
 
 
 def _blocked_bits(blocked, n_dirs):
